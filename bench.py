@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Headline benchmark: pretrain images/sec of bicaptioning_R_50_L1_H1024 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the line; --dump-outputs DIR also writes what the last timed step
+computed (DIR/<name>.npy); --full adds the secondary legs listed below.
 
 One "step" = the reference's whole training-step body (scripts/pretrain_virtex.py:145-163):
 zero_grad -> forward (dropout 0.1 on) -> backward -> gradient all-reduce (N > 1) -> clip 10.0 ->
@@ -10,7 +13,7 @@ SGD(m .9, per-tensor lr/wd) -> Lookahead(5, .5) -> LR schedule (fused HIP optimi
 Workload at N=1 = BASELINE.json configs[1]: bf16 compute, 256 images per GPU.  For N > 1 the
 driver launches this file under torch.distributed.run, one rank per GPU (weak scaling).
 
-Rank 0 prints ONE JSON line; besides the contract fields it carries
+Rank 0 prints ONE JSON line; besides the contract fields it carries "step_mfma" and, with --full, the other objects:
   "roofline"     : the step's dominant kernel -- the kernel (contraction-kernel instantiation, or BatchNorm / LayerNorm
                    / embedding / loss / optimizer ... kernel) with the largest summed time -- algorithmic FLOPs and bytes /
                    HIP-event time per launch measured live on the launch streams (vtx_profile_start/stop), against the
@@ -51,6 +54,13 @@ def parse(argv=None):
     ap.add_argument("--textual", default="transdec_postnorm::L1_H1024_A16_F4096")
     ap.add_argument("--visual", default="torchvision::resnet50")
     ap.add_argument("--dropout", type=float, default=0.1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary leg: the eager step beside the replayed one, roofline, "
+                         "bf16-vs-fp32 fidelity, CPU baseline (each still has its --no-... switch).  Without it the run sets up, "
+                         "warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32): loss, and the same seeded sample of "
+                         "the updated parameters and of the gradients they were updated with (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--stock-pytorch-baseline", action="store_true",
                     help="also time the reference's module graph (the oracle port) on this GPU through stock PyTorch-ROCm "
@@ -464,6 +474,29 @@ def stock_pytorch_baseline(batch, dev, steps=10, warmup=3, visual="torchvision::
                     f"B={batch}, {steps} steps after {warmup} warm-up steps (MIOpen's solver search is in warmup_s)"}
 
 
+DUMP_SAMPLE_ELEMS = 4 << 20      # per array: 16 MiB of float32, so a dump stays far below 64 MB
+
+
+def dump_outputs(path, loss, opt, buckets):
+    """What a caller of the timed step holds after its last step: the loss it returned, the parameters it updated (the
+    optimizer's flat fp32 buffer the model's parameters live in) and the gradients it updated them with (the flat fp32 buffer
+    of the gradient buckets).  The two flat buffers have one element per parameter element (69.5 M in the default workload):
+    beyond DUMP_SAMPLE_ELEMS elements the SAME seeded, sorted sample of positions is written for both, identical from run to
+    run and from build to build."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    n = opt.flat_p.numel()
+    idx = None
+    if n > DUMP_SAMPLE_ELEMS:
+        idx = torch.randint(0, n, (DUMP_SAMPLE_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values.to(opt.flat_p.device)
+    arrays = {"loss": loss.detach().reshape(1), "parameters": opt.flat_p, "gradients": buckets.flat}
+    for name, t in arrays.items():
+        if idx is not None and t.numel() == n:
+            t = t[idx]
+        np.save(os.path.join(path, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
+
+
 def set_streams(concurrent: bool):
     """Turn the side streams of the step on / off at run time (virtex_amd/streams.py, models.HEAD_STREAMS)."""
     from virtex_amd import models, streams
@@ -570,7 +603,8 @@ def main(argv=None, device=None, backend=None):
     vd.synchronize()
     device_sync()
     from virtex_amd import ops
-    live = a.roofline_live and not a.no_roofline and rank == 0
+    roofline = a.full and not a.no_roofline
+    live = a.roofline_live and roofline and rank == 0
     if live:
         ops.profile_start()
     t0 = time.perf_counter()
@@ -581,9 +615,12 @@ def main(argv=None, device=None, backend=None):
     vd.synchronize()
     device_sync()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, opt, buckets)
     eager_ms = None
     if gstep is not None:
         gstep.sync()
+    if gstep is not None and a.full:
         # the same step issued by its Python (what N > 1 and any training loop without a fixed batch shape run): timed beside
         # the replayed one, same process, same state -- `value` stays the replayed step, config.eager_ms_per_step says what
         # the difference is
@@ -622,7 +659,7 @@ def main(argv=None, device=None, backend=None):
     #   pass 2 (roofline_steps steps, only that class timed): its per-launch duration;
     #   pass 3 (streams back on, same class): what the same launches take while sharing the chip.
     survey = focused = concurrent = None
-    if not a.no_roofline and live_recs is None:
+    if roofline and live_recs is None:
         prof = rank == 0
         set_streams(False)
         step(0)
@@ -661,7 +698,7 @@ def main(argv=None, device=None, backend=None):
     # made rank-0's HERE, where they start to matter: before anything validation-like reads them.
     vd.broadcast_buffers(model)
     fid = None
-    if a.dtype == "bf16" and not a.no_fidelity:
+    if a.full and a.dtype == "bf16" and not a.no_fidelity:
         from virtex_amd import fidelity
         try:
             fid = fidelity.bf16_vs_fp32(model, batches[0], buckets)
@@ -709,7 +746,7 @@ def main(argv=None, device=None, backend=None):
             tf = ips * gflop / 1e3
             rec["step_mfma"] = {"gflop_per_image": gflop, "achieved_tflops": round(tf, 1),
                                 "peak_tflops": peak * world, "frac": round(tf / (peak * world), 4)}
-        if not a.no_roofline:
+        if roofline:
             default_workload = TABLED_WORKLOADS.get((a.batch, a.dtype, a.textual, a.visual, world, a.image_size, a.vocab_size))
             if live_recs is not None:
                 rec["roofline"] = step_roofline(live_recs, a.dtype, default_workload)
@@ -737,7 +774,7 @@ def main(argv=None, device=None, backend=None):
         from virtex_amd.modules import visual_backbones as vbm
         rec["config"]["bn_fusion"] = {"backward_sums_in_dgrad_epilogue": bool(vbm.FUSE_BN_BWD and a.dtype == "bf16"),
                                       "forward_statistics_in_conv_epilogue": bool(vbm.FUSE_BN_STATS and a.dtype == "bf16")}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(a.cpu_batch, a.cpu_steps)
         if world == 1 and a.stock_pytorch_baseline and dev.type == "cuda":
             del model, buckets, opt, batches                     # the product's memory back before the baseline allocates its own

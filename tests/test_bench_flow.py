@@ -13,7 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RUNNER = os.path.join(ROOT, "tests", "bench_flow_runner.py")
 ARGS = ["--steps", "2", "--warmup", "1", "--batch", "2", "--image-size", "64", "--vocab-size", "304", "--dtype", "bf16",
         "--textual", "transdec_postnorm::L1_H128_A2_F256", "--no-cpu-baseline", "--roofline-steps", "1",
-        "--launch", "eager"]      # (launch replay has its own tests: on the emulator its warm-up / validation / recording steps cost minutes)
+        "--launch", "eager",      # (launch replay has its own tests: on the emulator its warm-up / validation / recording steps cost minutes)
+        "--full"]                 # the secondary legs (roofline, fidelity, CPU baseline) run only on request
 REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
             "vs_baseline", "dtype", "data", "config", "roofline"}
 
@@ -50,6 +51,26 @@ def test_single_rank_flow():
     cpu = rec["cpu_baseline"]
     assert cpu["kind"] == "port" and cpu["value"] > 0 and cpu["cores"] >= 1 and cpu["unit"] == "images/sec"
     assert cpu["config1_bs2"]["value"] > 0
+
+
+def test_plain_run_times_the_steps_and_dumps_what_the_last_one_computed(tmp_path):
+    """Without --full: set-up, warm-up, the timed steps, the line -- no secondary leg.  --dump-outputs writes the last timed
+    step's loss, parameters and gradients as float32 .npy files (this toy model is small enough to be written whole)."""
+    import numpy as np
+    args = [x for x in ARGS if x != "--full"] + ["--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run([sys.executable, RUNNER, "--gpus", "1"] + args, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = _json_line(r.stdout)
+    assert (REQUIRED - {"roofline"}) <= set(rec) and rec["steps"] == 2 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    assert not {"roofline", "fidelity", "cpu_baseline", "stock_pytorch_baseline"} & set(rec)
+    # batch 2: images/sec from the timed steps alone (`value` is printed with two decimals: half a unit of the last one)
+    assert rec["value"] == pytest.approx(2 * 1e3 / rec["ms_per_step"], rel=1e-3, abs=0.005)
+    assert sorted(os.listdir(tmp_path / "out")) == ["gradients.npy", "loss.npy", "parameters.npy"]
+    out = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in ("loss", "parameters", "gradients")}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in out.values())
+    assert out["loss"].shape == (1,) and float(out["loss"][0]) == pytest.approx(rec["config"]["final_loss"], abs=1e-4)
+    assert out["parameters"].shape == out["gradients"].shape and out["parameters"].ndim == 1 and np.abs(out["gradients"]).max() > 0
+    assert sum(v.nbytes for v in out.values()) <= 64e6
 
 
 def test_two_rank_flow_does_not_deadlock_in_the_roofline_leg():

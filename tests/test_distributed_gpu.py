@@ -91,7 +91,7 @@ def test_bench_through_rccl_with_one_rank(payload, launch):
     import json
     args = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "8", "--image-size", "64", "--vocab-size", "1000",
             "--textual", "transdec_postnorm::L1_H128_A2_F256", "--no-cpu-baseline", "--roofline-steps", "1", "--dropout", "0.0",
-            "--launch", launch]         # replay (round 5): the recorded launch list carries the RCCL all-reduces and their waits
+            "--full", "--launch", launch]         # replay (round 5): the recorded launch list carries the RCCL all-reduces and their waits
     def run(extra_env):
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True,
