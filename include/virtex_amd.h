@@ -373,6 +373,31 @@ int vtx_cross_entropy_bwd(int dtype, const float* logits, long ld, const long lo
                           const float* lse, const float* loss_and_count, const float* grad_out,
                           void* dlogits, long ldd, int R, int V, int ignore_index, void* stream);
 
+/* ---- the classification pretraining head (csrc/classify.hip) ---------------------------
+ * Global average pool of the NHWC feature map, y[b][c] = mean_p x[b][p][c]: the
+ * visual_features.view(B, C, -1).permute(0, 2, 1).mean(dim=1) of LinearTextualHead.forward
+ * (virtex/modules/textual_heads.py:85-91) and its backward dx[b][p][c] = dy[b][c] / HW (aten::mean backward of the
+ * same lines).  x, dx: [B][HW][C], y, dy: [B][C], in `dtype`, sums in fp32; C % 8 == 0 and 16-byte aligned tensors,
+ * else VTX_ERR_SHAPE. */
+int vtx_gap_fwd(int dtype, const void* x, void* y, int B, int HW, int C, void* stream);
+int vtx_gap_bwd(int dtype, const void* dy, void* dx, int B, int HW, int C, void* stream);
+/* Set-valued ("K-hot") softmax cross-entropy: F.log_softmax + the per-instance loop (labels.unique(), `l not in
+ * ignore_indices`, mean of the picked log-probabilities) of ClassificationModel.forward
+ * (virtex/models/classification.py:75-96), and its autograd backward.
+ * logits fp32 [R][ld] (ld >= V; columns >= V are never read), labels int64 [R][L] (the padded label matrix), ignore:
+ * n_ignore <= 8 indices in HOST memory (passed to the kernel by value).  S_r = the distinct labels of row r that lie in
+ * [0, V) and are not ignored -- a label outside [0, V) is DROPPED, where the reference raises an index error -- K_r = |S_r|:
+ *   fwd: lse[R], kcount[R] = K_r, row_loss[r] = lse[r] - (1/K_r) sum_{v in S_r} logits[r][v], loss[0] = mean_r row_loss[r]
+ *        (summed in a fixed order; a row with K_r = 0 gives NaN like the reference's mean of an empty selection);
+ *   bwd: dlogits[r][v] = grad_out[0]/R * (exp(logits[r][v] - lse[r]) - [v in S_r]/K_r) in `dtype`, [R][ldd], columns
+ *        [V, ldd) written as zeros (the gradient GEMMs run on a class dimension padded to a multiple of 8).
+ * V <= 65536, L >= 1; V needs no divisibility. */
+int vtx_khot_ce_fwd(const float* logits, long ld, const long long* labels, int L, const int* ignore, int n_ignore,
+                    float* lse, float* kcount, float* row_loss, float* loss, int R, int V, void* stream);
+int vtx_khot_ce_bwd(int dtype, const float* logits, long ld, const long long* labels, int L, const int* ignore,
+                    int n_ignore, const float* lse, const float* kcount, const float* grad_out, void* dlogits,
+                    long ldd, int R, int V, void* stream);
+
 /* ---- tied output projection + cross-entropy, logits never in HBM (csrc/tied_ce.hip) -----
  * Replaces aten::linear of the tied output layer (textual_heads.py:199-200,277) + nn.CrossEntropyLoss(ignore_index)
  * (captioning.py:69,111-114,127-132) and their backward on the TRAINING path (the reference writes (B,T,V) fp32 logits).

@@ -64,7 +64,9 @@ def _run(cmd):
 # per-file flags of the HIP build.  conv3_bwd.hip: hipcc's SLP vectoriser turns the BatchNorm arithmetic of the transform and
 # the epilogue into v_pk_*_f32; the kernel is issue- / latency-bound with two waves per SIMD and runs 4 % faster without
 # (225.5 vs 234.1 us, profiles/r05_conv3_bwd_variants.txt)
-FILE_FLAGS = {"conv3_bwd.hip": ["-fno-slp-vectorize"]}
+# classify.hip: no packed fp32 arithmetic (v_pk_*_f32) in its streaming loops -- they are HBM-bound and gain nothing from it
+FILE_FLAGS = {"conv3_bwd.hip": ["-fno-slp-vectorize"],
+              "classify.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _compile_all(compiler, flags, objdir, hdr_mtime, verbose):

@@ -54,6 +54,7 @@ class TextualHeadFactory(Factory):
     PRODUCTS: Dict[str, Callable] = {
         "transdec_prenorm": partial(textual_heads.TransformerDecoderTextualHead, norm_first=True),
         "transdec_postnorm": partial(textual_heads.TransformerDecoderTextualHead, norm_first=False),
+        "none": textual_heads.LinearTextualHead,       # the classification tasks: no language modelling
     }
 
     @classmethod
@@ -75,15 +76,24 @@ class PretrainingModelFactory(Factory):
         "virtex": models.VirTexModel,
         "bicaptioning": models.BidirectionalCaptioningModel,
         "captioning": models.ForwardCaptioningModel,
+        "token_classification": models.TokenClassificationModel,
+        "multilabel_classification": models.MultiLabelClassificationModel,
     }
 
     @classmethod
     def from_config(cls, config):
+        """Model-specific keyword arguments as the reference chooses them (factories.py:445-466)."""
         _C = config
         visual = VisualBackboneFactory.from_config(_C)
         textual = TextualHeadFactory.from_config(_C)
-        kwargs = {"sos_index": _C.DATA.SOS_INDEX, "eos_index": _C.DATA.EOS_INDEX,
-                  "decoder": CaptionDecoderFactory.from_config(_C)}
+        kwargs = {}
+        if _C.MODEL.NAME in ("virtex", "captioning", "bicaptioning"):
+            kwargs = {"sos_index": _C.DATA.SOS_INDEX, "eos_index": _C.DATA.EOS_INDEX,
+                      "decoder": CaptionDecoderFactory.from_config(_C)}
+        elif _C.MODEL.NAME == "token_classification":      # the special tokens are no targets
+            kwargs = {"ignore_indices": [_C.DATA.UNK_INDEX, _C.DATA.SOS_INDEX, _C.DATA.EOS_INDEX, _C.DATA.MASK_INDEX]}
+        elif _C.MODEL.NAME == "multilabel_classification":
+            kwargs = {"ignore_indices": [0]}               # COCO's background category
         return cls.create(_C.MODEL.NAME, visual, textual, **kwargs)
 
 
@@ -130,9 +140,15 @@ def build_bicaptioning_model(visual: str = "torchvision::resnet50",
     return PretrainingModelFactory.create(model_name, vb, th, sos_index=1, eos_index=2, decoder=None)
 
 
-def register(reference_factories=None) -> List[str]:
+# the products of the classification pretraining tasks (`task_ablations` configurations)
+CLASSIFICATION_PRODUCTS = ("none", "token_classification", "multilabel_classification")
+
+
+def register(reference_factories=None, classification: bool = False) -> List[str]:
     """Install the native products into the reference's registries (drop-in).  Pass the imported
-    ``virtex.factories`` module, or let it be imported.  Returns the keys that were replaced."""
+    ``virtex.factories`` module, or let it be imported.  Returns the keys that were replaced.
+    classification=True also installs the classification tasks' head and models (CLASSIFICATION_PRODUCTS); without it
+    those keys stay the reference's own, as they always have after this call."""
     if reference_factories is None:
         import virtex.factories as reference_factories  # noqa: the reference package
     replaced = []
@@ -141,6 +157,8 @@ def register(reference_factories=None) -> List[str]:
                          (PretrainingModelFactory, reference_factories.PretrainingModelFactory),
                          (CaptionDecoderFactory, reference_factories.CaptionDecoderFactory)):
         for key, product in ours.PRODUCTS.items():
+            if key in CLASSIFICATION_PRODUCTS and not classification:
+                continue
             theirs.PRODUCTS[key] = product
             replaced.append(f"{theirs.__name__}.{key}")
     return replaced

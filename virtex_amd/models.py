@@ -11,10 +11,14 @@ into the tied-projection + cross-entropy op (`_FusedTiedCrossEntropyFn`, csrc/ti
 partials, the backward recomputes the projection and emits the logit gradient in the compute
 dtype.  The eval branch and ``decoding_step`` keep the reference semantics through
 ``textual(...)`` which returns logits.
+
+``ClassificationModel`` / ``TokenClassificationModel`` / ``MultiLabelClassificationModel`` (at the end of the file) are the
+drop-ins for /root/reference/virtex/models/classification.py: ``LinearTextualHead`` under the K-hot cross-entropy of
+csrc/classify.hip.
 """
 import copy
 import functools
-from typing import Any, Dict
+from typing import Any, Dict, List
 
 import torch
 from .replay import traced_backward
@@ -338,3 +342,87 @@ class BidirectionalCaptioningModel(CaptioningModel):
 
 # Convenient handle, as in the reference (captioning.py:282-283).
 VirTexModel = BidirectionalCaptioningModel
+
+
+class _KHotCrossEntropyFn(torch.autograd.Function):
+    """mean_b ( logsumexp(logits[b, :V]) - mean_{v in S_b} logits[b, v] ), S_b = the distinct labels of instance b that are not
+    ignored: the reference's per-instance loop with .unique() and one host sync per label (classification.py:75-96) as two
+    kernel launches (csrc/classify.hip).  logits: (B, ld) fp32 with ld >= V -- the padded logits of LinearTextualHead."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore, V):
+        labels = labels.contiguous()
+        loss, lse, kcount = ops.khot_ce_fwd(logits, labels, ignore, V)
+        ctx.save_for_backward(logits, labels, lse, kcount)
+        ctx.cfg = (ignore, V)
+        return loss[0].clone()
+
+    @staticmethod
+    @traced_backward
+    def backward(ctx, gout):
+        logits, labels, lse, kcount = ctx.saved_tensors
+        ignore, V = ctx.cfg
+        g = gout.reshape(1).to(torch.float32).contiguous()
+        # in the logits' own dtype (what autograd hands on unchanged); the head casts it for its gradient GEMMs
+        return ops.khot_ce_bwd(logits, labels, lse, kcount, g, logits.dtype, ignore, V), None, None, None
+
+
+class ClassificationModel(nn.Module):
+    """Drop-in for the reference's ``ClassificationModel`` (virtex/models/classification.py:12-108): same constructor,
+    attribute tree (``visual``, ``textual``, ``ignore_indices``) and output dict ``{"loss", "loss_components":
+    {"classification"}, ["predictions"]}``.  ``batch["labels"]`` is the padded (B, L) label matrix."""
+
+    def __init__(self, visual: VisualBackbone, textual: TextualHead, ignore_indices: List[int]):
+        super().__init__()
+        self.visual = visual
+        self.textual = textual
+        self.ignore_indices = ignore_indices
+
+    def forward(self, batch: Dict[str, torch.Tensor]) -> Dict[str, Any]:
+        dt = getattr(self.textual, "compute_dtype", None)
+        if dt is not None and hasattr(self.visual, "weight_plan"):
+            ops.prep_many(list(self.visual.weight_plan()) + list(self.textual.weight_plan()), dt)
+        if hasattr(self.textual, "defer_join"):
+            self.textual.defer_join = bool(self.training and torch.is_grad_enabled() and isinstance(self.visual, VisualBackbone)
+                                           and any(p.requires_grad for p in self.visual.parameters()))
+        visual_features = self.visual(batch["image"])
+        V = self.textual.vocab_size
+        logits = self.textual.padded_logits(visual_features) if hasattr(self.textual, "padded_logits") \
+            else self.textual(visual_features)
+        loss = _KHotCrossEntropyFn.apply(logits, batch["labels"], tuple(int(i) for i in self.ignore_indices), V)
+        output_dict: Dict[str, Any] = {"loss": loss, "loss_components": {"classification": loss.clone().detach()}}
+        if not self.training:       # top-10 classes for logging; off the training path
+            output_dict["predictions"] = logits[:, :V].topk(k=10, dim=1)[1]
+        return output_dict
+
+    def _predict(self, batch):
+        was_training = self.training
+        self.eval()
+        with torch.no_grad():
+            predictions = self.forward(batch)["predictions"]
+        self.train(was_training)
+        return predictions
+
+
+class TokenClassificationModel(ClassificationModel):
+    """Targets: the set of caption tokens, special tokens ignored (reference: classification.py:111-140)."""
+
+    def log_predictions(self, batch: Dict[str, torch.Tensor], tokenizer) -> str:
+        lines = []
+        for tokens, preds in zip(batch["caption_tokens"], self._predict(batch)):
+            # the predictions are an unordered set of tokens: decoded one by one, so that metaspace and special tokens survive
+            words = " ".join(tokenizer.id_to_token(p) for p in preds.tolist())
+            lines.append(f"\n    Caption tokens : {tokenizer.decode(tokens.tolist())}\n    Predictions (f): {words}\n")
+        return "".join(lines)
+
+
+class MultiLabelClassificationModel(ClassificationModel):
+    """Targets: the set of COCO categories in the image, background (0) ignored (reference: classification.py:143-174)."""
+
+    def log_predictions(self, batch: Dict[str, torch.Tensor], tokenizer=None) -> str:
+        lines = []
+        for tokens, preds in zip(batch["caption_tokens"], self._predict(batch)):
+            truth = sorted(t for t in tokens.tolist() if t != 0)
+            lines.append(f"\n    COCO Instance IDs (GT)   : {truth}\n"
+                         f"    COCO Instance IDs (Pred) : {sorted(preds.tolist()[: len(truth)])}\n")
+        return "".join(lines)

@@ -126,6 +126,114 @@ class TextualHead(nn.Module):
         return self.hidden_size
 
 
+class LinearTextualHead(TextualHead):
+    """Global average pool + one linear layer over the vocabulary: the head of the classification pretraining tasks
+    (reference: virtex/modules/textual_heads.py:46-95; state-dict keys ``output.weight``, ``output.bias``).  ``nn.Linear`` is
+    a parameter container only: pool, projection and their backward are one autograd Function on csrc/classify.hip and the
+    MFMA GEMMs.  The GEMMs want a class dimension that is a multiple of 8: the copies of the weight and the bias they read are
+    zero-padded to Vp = round_up(V, 8) rows (COCO multilabel: 81 -> 88), the parameters stay (V, C) and (V,).
+
+    Precision: the logits feed a loss, so the FORWARD projection is an fp32 GEMM on the fp32 master weight -- B x C x V, a third
+    of the head's arithmetic -- and the pool runs in the dtype the features arrive in (no
+    conversion copy).  ``compute_dtype`` is the operand type of the two backward GEMMs (d logits, pooled features, W^T), where
+    bf16's 2^-9 stays inside the gradient bounds; with bf16 operands in the forward the loss itself is off by 2e-5 .. 4e-5."""
+
+    def __init__(self, visual_feature_size: int, vocab_size: int, **kwargs):
+        super().__init__(visual_feature_size, vocab_size, visual_feature_size)
+        self.output = nn.Linear(visual_feature_size, vocab_size)
+        self.compute_dtype = kwargs.get("compute_dtype", torch.bfloat16)
+        # set by the model when the backbone's backward runs after this head's and joins the weight-gradient stream itself
+        self.defer_join = False
+
+    def padded_logits(self, visual_features):
+        """(B, Vp) fp32 logits; the columns [V, Vp) are padding (zeros) that the K-hot loss kernels never read."""
+        return _LinearHeadFn.apply(visual_features, self.output.weight, self.output.bias, self.compute_dtype, self.defer_join)
+
+    def forward(self, visual_features, caption_tokens=None, caption_lengths=None):
+        """(B, C, h, w) visual grid -> (B, V) fp32 logits; the caption arguments are ignored, as in the reference."""
+        logits = self.padded_logits(visual_features)
+        return logits if logits.shape[1] == self.vocab_size else logits[:, : self.vocab_size]
+
+    def weight_plan(self):
+        return []       # the one compute copy (W^T for the input gradient) is made on first use in backward
+
+
+def _linear_head_weights(weight, bias, dt, want_wt=False):
+    """What LinearTextualHead's GEMMs read, rows [V, Vp) zero: (fp32 weight [Vp, C], fp32 bias [Vp], wt [C, Vp] in `dt` or None).
+    V % 8 == 0: the parameters themselves and ops.prepped's transposed copy; else padded copies cached on the weight until
+    either parameter changes."""
+    V, C = weight.shape
+    Vp = (V + 7) // 8 * 8
+    if Vp == V:
+        wt = ops.prepped(weight, dt, want_w=False)[1].view(C, V) if want_wt else None
+        return weight.detach(), bias.detach(), wt
+    store = weight.__dict__.setdefault("_vtx_prep", {})
+    stamp = (weight._version, weight.data_ptr(), bias._version, bias.data_ptr())
+    e = store.get((dt, "rows", Vp))
+    if e is None or e[0] != stamp:
+        w32 = torch.zeros(Vp, C, dtype=torch.float32, device=weight.device)
+        w32[:V] = weight.detach()
+        b = torch.zeros(Vp, dtype=torch.float32, device=weight.device)
+        b[:V] = bias.detach()
+        e = store[(dt, "rows", Vp)] = [stamp, w32, b, None]
+    if want_wt and e[3] is None:
+        e[3] = ops.weight_prep(e[1], dt, want_w=False)[1].view(C, Vp)
+    return e[1], e[2], e[3]
+
+
+class _LinearHeadFn(torch.autograd.Function):
+    """logits = mean_p(visual grid) @ W^T + b on the padded class dimension (reference: textual_heads.py:85-95)."""
+
+    @staticmethod
+    def forward(ctx, visual_features, weight, bias, dt, defer_join):
+        B, C, h, w = visual_features.shape
+        grid = visual_features.permute(0, 2, 3, 1)          # zero-copy for NHWC-physical input
+        if grid.dtype not in (torch.float32, torch.bfloat16):
+            grid = grid.to(dt)
+        pooled = ops.gap_fwd(grid.contiguous().view(B, h * w, C))       # in the features' own dtype
+        p32 = pooled if pooled.dtype == torch.float32 else pooled.float()
+        w32, b32, _ = _linear_head_weights(weight, bias, dt)
+        # the backward GEMMs' copy of the pooled features
+        ctx.pooled = pooled if pooled.dtype == dt else (p32 if dt == torch.float32 else ops.cast_from_f32(p32, dt))
+        ctx.owner, ctx.dt, ctx.defer_join = (weight, bias), dt, defer_join
+        ctx.vshape, ctx.needs_vis_grad = visual_features.shape, visual_features.requires_grad
+        return ops.gemm_nt(p32, w32, bias=b32, out_f32=True)
+
+    @staticmethod
+    @traced_backward
+    def backward(ctx, d):
+        weight, bias = ctx.owner
+        dt, pooled = ctx.dt, ctx.pooled
+        V, Vp = weight.shape[0], d.shape[1]
+        if d.dtype != dt:
+            d = ops.cast_from_f32(d.contiguous(), dt) if d.dtype == torch.float32 else d.to(dt)
+        d = d.contiguous()
+        dev = d.device
+        if Vp == V:
+            dW, rW = _sink_or_zeros(weight)
+            db, rb = _sink_or_zeros(bias)
+        else:       # gradients on the padded class dimension, the parameters' rows sliced out of them
+            dW = torch.zeros(Vp, weight.shape[1], dtype=torch.float32, device=dev)
+            db = torch.zeros(Vp, dtype=torch.float32, device=dev)
+            rW, rb = dW[:V], db[:V]
+        on_side = rW is None and rb is None
+        if on_side:
+            with wgrad_stream(dev, d, pooled):
+                ops.gemm_tn_acc(d, pooled, dW)
+                ops.colsum_acc(d, db)
+        else:
+            ops.gemm_tn_acc(d, pooled, dW)
+            ops.colsum_acc(d, db)
+        dvis = None
+        if ctx.needs_vis_grad:
+            _, _, wt = _linear_head_weights(weight, bias, dt, want_wt=True)
+            Bv, C, h, w = ctx.vshape
+            dvis = ops.gap_bwd(ops.gemm_nt(d, wt), h * w).view(Bv, h, w, C).permute(0, 3, 1, 2)
+        if on_side and not ctx.defer_join:
+            wgrad_stream.join(dev)
+        return dvis, rW, rb, None, None
+
+
 class TransformerDecoderTextualHead(TextualHead):
     def __init__(self, visual_feature_size: int, vocab_size: int, hidden_size: int, num_layers: int,
                  attention_heads: int, feedforward_size: int, dropout: float = 0.1,

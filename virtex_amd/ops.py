@@ -749,6 +749,58 @@ def cross_entropy_bwd(logits, targets, lse, lc, grad_out, dtype, ignore_index=0)
     return d
 
 
+# ---------------------------------------------------------------------------------------
+# the classification head (csrc/classify.hip)
+def gap_fwd(x):
+    """Global average pool of an NHWC map: x (B, ..., C) contiguous -> (B, C), same dtype, fp32 sums."""
+    _chk(x, "x")
+    B, C = x.shape[0], x.shape[-1]
+    y = torch.empty(B, C, dtype=x.dtype, device=x.device)
+    call("vtx_gap_fwd", c_int(dtype_code(x.dtype)), ptr(x), ptr(y), c_int(B), c_int(x.numel() // (B * C)), c_int(C), stream_ptr(x))
+    return y
+
+
+def gap_bwd(dy, HW):
+    """dx (B, HW, C) = dy (B, C) / HW at every position."""
+    _chk(dy, "dy")
+    B, C = dy.shape
+    dx = torch.empty(B, HW, C, dtype=dy.dtype, device=dy.device)
+    call("vtx_gap_bwd", c_int(dtype_code(dy.dtype)), ptr(dy), ptr(dx), c_int(B), c_int(HW), c_int(C), stream_ptr(dy))
+    return dx
+
+
+def _ignore_array(ignore):
+    ignore = [int(i) for i in ignore]
+    return (_lib.ctypes.c_int * max(len(ignore), 1))(*ignore), c_int(len(ignore))
+
+
+def khot_ce_fwd(logits, labels, ignore=(), V=None):
+    """K-hot cross-entropy: logits fp32 [R, ld] (the first V columns count), labels int64 [R, L], ignore: up to 8 indices.
+    Returns (loss[1], lse[R], kcount[R])."""
+    R, ld = logits.shape
+    V = ld if V is None else V
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and labels.dim() == 2 and labels.shape[0] == R
+    _chk(labels, "labels", torch.int64)
+    lse, kcount, row_loss = (torch.empty(R, dtype=torch.float32, device=logits.device) for _ in range(3))
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    ign, n = _ignore_array(ignore)
+    call("vtx_khot_ce_fwd", ptr(logits), c_long(logits.stride(0)), ptr(labels), c_int(labels.shape[1]), ign, n, ptr(lse),
+         ptr(kcount), ptr(row_loss), ptr(loss), c_int(R), c_int(V), stream_ptr(logits))
+    return loss, lse, kcount
+
+
+def khot_ce_bwd(logits, labels, lse, kcount, grad_out, dtype, ignore=(), V=None):
+    """d(logits) [R, ld] in `dtype`; the columns [V, ld) are zeros."""
+    R, ld = logits.shape
+    V = ld if V is None else V
+    _chk(grad_out, "grad_out", torch.float32); _chk(labels, "labels", torch.int64)
+    d = torch.empty(R, ld, dtype=dtype, device=logits.device)
+    ign, n = _ignore_array(ignore)
+    call("vtx_khot_ce_bwd", c_int(dtype_code(dtype)), ptr(logits), c_long(logits.stride(0)), ptr(labels), c_int(labels.shape[1]),
+         ign, n, ptr(lse), ptr(kcount), ptr(grad_out), ptr(d), c_long(ld), c_int(R), c_int(V), stream_ptr(logits))
+    return d
+
+
 _tied_ce_ws = {}
 
 
