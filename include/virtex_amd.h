@@ -415,6 +415,27 @@ int vtx_tied_ce_bwd(int dtype, int R, int V, int H, const void* hidden, long ldh
                     const float* bias, const long long* targets, int ignore_index, const float* lse,
                     const float* loss_and_count, const float* grad_out, void* dlogits, void* stream);
 
+/* ---- masked language modelling: the labelled rows only (csrc/masked_ce.hip) -----------------
+ * The reference's MaskedLMModel (virtex/models/masked_lm.py:33,67-72) runs the tied projection and nn.CrossEntropyLoss(
+ * ignore_index = padding_idx) over all R = B*T rows, of which about one in six carries a label.  These three kernels compact
+ * the labelled rows into [cap][H]; vtx_tied_ce_fwd / _bwd, vtx_gemm_nt and vtx_gemm_tn_acc then run on cap rows, unchanged.
+ * "Labelled": label != ignore_index && 0 <= label < V (the rule of vtx_tied_ce_fwd).
+ * vtx_label_compact: labels[R] int64 -> rows[R] int32 (rows[i] = index of the i-th labelled row, ascending; entries from
+ *   count on are not written), slot[R] int32 (position of row r in that list, or -1), count[1] int32.  One launch, no atomics,
+ *   bit-reproducible.  1 <= R <= 1 048 576, else VTX_ERR_SHAPE.
+ * vtx_rows_pack: hidden[.][H] dtype (row stride ldh; must have the R rows that rows[] was made for), rows / count as above
+ *   (count is read on the device) -> packed[cap][H] dense, packed_targets[cap] int64: row i < min(count, cap) is
+ *   hidden[rows[i]] with labels[rows[i]], every other row is zeros with target ignore_index.  count > cap: packed row 0 is
+ *   filled with NaN, so that the loss over the packed rows is NaN and not a truncated mean.
+ * vtx_rows_unpack: dfull[r][0..H) (row stride ldd) = dpacked[slot[r]] where 0 <= slot[r] < cap, else zeros; every row of
+ *   dfull is written once.
+ * H and the row strides: multiples of 8 (bf16) / 4 (fp32), operands 16-byte aligned (as vtx_tied_ce_fwd requires), else
+ * VTX_ERR_SHAPE; copies are bit-exact. */
+int vtx_label_compact(const long long* labels, int ignore_index, int V, int* rows, int* slot, int* count, int R, void* stream);
+int vtx_rows_pack(int dtype, const void* hidden, long ldh, const long long* labels, const int* rows, const int* count, int cap,
+                  void* packed, long long* packed_targets, int ignore_index, int H, void* stream);
+int vtx_rows_unpack(int dtype, const void* dpacked, const int* slot, int cap, void* dfull, long ldd, int R, int H, void* stream);
+
 /* ---- one beam-search step on the device (csrc/beam.hip) ----------------------------------
  * Replaces the aten::log_softmax / scatter_ / where / topk / gather chain and the per-row Python loop of
  * virtex/utils/beam_search.py:115-228.  logits:[rows = images*beams_in][V] fp32 (row stride ld); last:[rows] int64 the

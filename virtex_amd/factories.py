@@ -78,6 +78,7 @@ class PretrainingModelFactory(Factory):
         "captioning": models.ForwardCaptioningModel,
         "token_classification": models.TokenClassificationModel,
         "multilabel_classification": models.MultiLabelClassificationModel,
+        "masked_lm": models.MaskedLMModel,             # no model kwargs, as in the reference (factories.py:463-464)
     }
 
     @classmethod
@@ -144,11 +145,16 @@ def build_bicaptioning_model(visual: str = "torchvision::resnet50",
 CLASSIFICATION_PRODUCTS = ("none", "token_classification", "multilabel_classification")
 
 
-def register(reference_factories=None, classification: bool = False) -> List[str]:
+# the masked language modelling task: the model only (its head is the transformer decoder without the causal mask)
+MASKED_LM_PRODUCTS = ("masked_lm",)
+
+
+def register(reference_factories=None, classification: bool = False, masked_lm: bool = False) -> List[str]:
     """Install the native products into the reference's registries (drop-in).  Pass the imported
     ``virtex.factories`` module, or let it be imported.  Returns the keys that were replaced.
     classification=True also installs the classification tasks' head and models (CLASSIFICATION_PRODUCTS); without it
-    those keys stay the reference's own, as they always have after this call."""
+    those keys stay the reference's own, as they always have after this call.  masked_lm=True does the same for
+    MASKED_LM_PRODUCTS."""
     if reference_factories is None:
         import virtex.factories as reference_factories  # noqa: the reference package
     replaced = []
@@ -158,6 +164,8 @@ def register(reference_factories=None, classification: bool = False) -> List[str
                          (CaptionDecoderFactory, reference_factories.CaptionDecoderFactory)):
         for key, product in ours.PRODUCTS.items():
             if key in CLASSIFICATION_PRODUCTS and not classification:
+                continue
+            if key in MASKED_LM_PRODUCTS and not masked_lm:
                 continue
             theirs.PRODUCTS[key] = product
             replaced.append(f"{theirs.__name__}.{key}")

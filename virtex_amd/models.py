@@ -14,7 +14,8 @@ dtype.  The eval branch and ``decoding_step`` keep the reference semantics throu
 
 ``ClassificationModel`` / ``TokenClassificationModel`` / ``MultiLabelClassificationModel`` (at the end of the file) are the
 drop-ins for /root/reference/virtex/models/classification.py: ``LinearTextualHead`` under the K-hot cross-entropy of
-csrc/classify.hip.
+csrc/classify.hip.  ``MaskedLMModel`` is the drop-in for the reference's virtex/models/masked_lm.py: the same decoder without
+the causal mask, its tied projection and loss on the labelled rows only (csrc/masked_ce.hip).
 """
 import copy
 import functools
@@ -342,6 +343,162 @@ class BidirectionalCaptioningModel(CaptioningModel):
 
 # Convenient handle, as in the reference (captioning.py:282-283).
 VirTexModel = BidirectionalCaptioningModel
+
+
+# Masked LM: tied projection + cross-entropy on the labelled rows only (csrc/masked_ce.hip).  "0" selects the dense fused path --
+# _FusedTiedCrossEntropyFn's kernels over all B*T rows with masked_labels as targets -- for A/B runs and as the fallback.
+COMPACT_MASKED_CE = os.environ.get("VIRTEX_AMD_COMPACT_MASKED_CE", "1") != "0"
+# rows the compacted GEMMs run on = the labelled rows rounded up to this (exact mode); also the smallest capacity
+MASKED_CE_GRANULE = 128
+# Exact mode counts the labelled rows on a side stream at the start of forward.  That stream waits for what the compute stream
+# holds at that moment, because loaders copy a batch to the device asynchronously ON the compute stream.  "1": the caller
+# guarantees the labels are resident when forward is called (a prefetching loader): the count then waits for nothing.
+MASKED_LABELS_RESIDENT = os.environ.get("VIRTEX_AMD_MASKED_LABELS_RESIDENT", "0") != "0"
+
+_label_streams = {}
+
+
+class _LabelCount:
+    """Exact mode: compaction + the 4-byte readback of the count on a stream of their own, launched before the backbone; `get()`
+    synchronises THAT stream only, after the forward pass has been enqueued -- the compute queue is never drained."""
+
+    def __init__(self, labels, padding_idx, V):
+        dev = labels.device
+        if dev.type != "cuda":
+            self.parts, self.event = ops.label_compact(labels, padding_idx, V), None
+            return
+        side = _label_streams.get(dev)
+        if side is None:
+            side = _label_streams[dev] = torch.cuda.Stream(device=dev)
+        if not MASKED_LABELS_RESIDENT:
+            side.wait_stream(torch.cuda.current_stream(dev))
+        labels.record_stream(side)
+        with torch.cuda.stream(side):
+            self.parts = ops.label_compact(labels, padding_idx, V)
+            self.host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+            self.host.copy_(self.parts[2], non_blocking=True)
+            self.event = torch.cuda.Event()
+            self.event.record(side)
+
+    def get(self):
+        """(rows, slot, count) usable on the current stream, and the count as a Python int"""
+        if self.event is None:
+            return self.parts, int(self.parts[2].item())
+        self.event.synchronize()
+        cur = torch.cuda.current_stream(self.parts[0].device)
+        for t in self.parts:
+            t.record_stream(cur)
+        return self.parts, int(self.host.item())
+
+
+class _MaskedTiedCrossEntropyFn(torch.autograd.Function):
+    """mean_{labels[b,t] != pad} CE(hidden[b,t] @ words^T + bias, labels[b,t]) (reference: masked_lm.py:67-72 on
+    textual_heads.py:277 logits), without logits in HBM.  cap = int: compact -> pack -> tied_ce_fwd on [cap][H]; backward
+    tied_ce_bwd -> gemm_nt -> unpack, the tied matrix' gradient contracts over cap rows.  cap = None: the dense fused path
+    over all B*T rows.  parts: (rows, slot, count) when the caller has compacted the labels already."""
+
+    @staticmethod
+    def forward(ctx, hidden, weight, bias, labels, padding_idx, cap, parts):
+        B, T, H = hidden.shape
+        dt, V = hidden.dtype, weight.shape[0]
+        h2 = hidden.reshape(B * T, H)
+        targets = labels.reshape(-1).contiguous()
+        slot = None
+        if cap is not None:
+            rows, slot, count = parts if parts is not None else ops.label_compact(targets, padding_idx, V)
+            h2, targets = ops.rows_pack(h2, targets, rows, count, cap, padding_idx)
+        w, _ = ops.prepped(weight, dt, want_wt=False)
+        lc, lse = ops.tied_ce_fwd(h2, w.view(V, H), bias.detach(), targets, padding_idx)
+        ctx.weight_param, ctx.bias_param = weight, bias
+        ctx.save_for_backward(h2, targets, lse, lc, slot)
+        ctx.cfg = (B, T, H, V, padding_idx, dt)
+        return lc[0].clone()
+
+    @staticmethod
+    @traced_backward
+    def backward(ctx, gout):
+        h2, targets, lse, lc, slot = ctx.saved_tensors
+        B, T, H, V, padding_idx, dt = ctx.cfg
+        g = gout.reshape(1).to(torch.float32).contiguous()
+        w, wt = ops.prepped(ctx.weight_param, dt)
+        d = ops.tied_ce_bwd(h2, w.view(V, H), ctx.bias_param.detach(), targets, lse, lc, g, padding_idx)     # (cap | B*T, V)
+        dh = ops.gemm_nt(d, wt.view(H, V))
+        if slot is not None:
+            dh = ops.rows_unpack(dh, slot)
+        rW, rb = tied_projection_grads(d, h2, ctx.weight_param, ctx.bias_param)
+        return dh.view(B, T, H), rW, rb, None, None, None, None
+
+
+class MaskedLMModel(nn.Module):
+    """Drop-in for the reference's ``MaskedLMModel`` (virtex/models/masked_lm.py:11-106): same two positional arguments,
+    attributes (``visual``, ``textual``, ``padding_idx``, ``loss``), output dict ``{"loss", "loss_components": {"masked_lm"},
+    ["predictions"]}`` and ``log_predictions``.  The head must have been built with ``mask_future_positions=False``
+    (TextualHeadFactory.from_config derives that from the model name).
+
+    The projection and the loss run on the labelled rows only (csrc/masked_ce.hip), ``cap`` rows instead of B*T:
+      * ``label_capacity=None`` (default), exact: the number of labelled rows is read back (4 bytes, on a stream of its own,
+        before the backbone is enqueued) and cap = that count rounded up to MASKED_CE_GRANULE.  One host wait per step:
+        not recordable by virtex_amd.replay / graph.
+      * ``label_capacity=int``, static: fixed shapes and no readback.  A batch with MORE labelled rows than the capacity
+        returns a NaN loss (the pack kernel poisons a row), never a truncated mean.  ``B * ceil((T - 2) * 0.15)`` is the
+        reference dataset's own bound (virtex/data/datasets/masked_lm.py:73-76: 5 per caption at T = 30)."""
+
+    def __init__(self, visual: VisualBackbone, textual: TextualHead, label_capacity: int = None):
+        super().__init__()
+        self.visual = visual
+        self.textual = textual
+        self.padding_idx = self.textual.padding_idx
+        self.label_capacity = label_capacity
+        self.loss = nn.CrossEntropyLoss(ignore_index=self.padding_idx)  # kept for API parity
+
+    def forward(self, batch: Dict[str, torch.Tensor]) -> Dict[str, Any]:
+        labels = batch["masked_labels"].contiguous()
+        V, pad = self.textual.vocab_size, self.padding_idx
+        compact = COMPACT_MASKED_CE or not self.training
+        counted = None
+        if compact and self.label_capacity is None:
+            counted = _LabelCount(labels.view(-1), pad, V)           # first: it overlaps everything below
+        dt = getattr(self.textual, "compute_dtype", None)
+        if dt is not None and hasattr(self.textual, "weight_plan"):     # one launch for all the compute copies of the step
+            ops.prep_many(list(self.visual.weight_plan() if hasattr(self.visual, "weight_plan") else [])
+                          + list(self.textual.weight_plan()), dt)
+        emb = getattr(self.textual, "embedding", None)
+        if emb is not None and hasattr(emb, "defer_join"):
+            emb.defer_join = bool(self.training and torch.is_grad_enabled() and isinstance(self.visual, VisualBackbone)
+                                  and any(p.requires_grad for p in self.visual.parameters()))
+        visual_features = self.visual(batch["image"])
+        hidden = self.textual.features(visual_features, batch["caption_tokens"], batch["caption_lengths"])
+        cap, parts = self.label_capacity, None
+        if counted is not None:
+            parts, count = counted.get()
+            cap = max(1, -(-count // MASKED_CE_GRANULE)) * MASKED_CE_GRANULE
+        if self.training:
+            loss = _MaskedTiedCrossEntropyFn.apply(hidden, self.textual.output.weight, self.textual.output.bias, labels, pad,
+                                                   cap if compact else None, parts)
+            return {"loss": loss, "loss_components": {"masked_lm": loss.clone().detach()}}
+        # eval: logits of the packed rows only; arg-max placed back, padding_idx elsewhere (masked_lm.py:79-84)
+        B, T, H = hidden.shape
+        rows, slot, count = parts if parts is not None else ops.label_compact(labels.view(-1), pad, V)
+        packed, targets = ops.rows_pack(hidden.reshape(B * T, H), labels.view(-1), rows, count, cap, pad)
+        w, _ = ops.prepped(self.textual.output.weight, hidden.dtype, want_wt=False)
+        logits = ops.gemm_nt(packed, w.view(V, H), bias=self.textual.output.bias.detach(), out_f32=True)
+        lc, _ = ops.cross_entropy_fwd(logits, targets, pad)
+        loss = lc[0].clone()
+        best = torch.argmax(logits, dim=-1)[slot.clamp(0, cap - 1).long()]
+        predictions = torch.where((slot >= 0) & (slot < cap), best, torch.full_like(best, pad)).view(B, T)
+        return {"loss": loss, "loss_components": {"masked_lm": loss.clone().detach()}, "predictions": predictions}
+
+    def log_predictions(self, batch: Dict[str, torch.Tensor], tokenizer) -> str:
+        self.eval()
+        with torch.no_grad():
+            predictions = self.forward(batch)["predictions"]
+        self.train()
+        lines = []
+        for tokens, labels, preds in zip(batch["caption_tokens"], batch["masked_labels"], predictions):
+            lines.append(f"\n    Caption tokens : {tokenizer.decode(tokens.tolist())}\n"
+                         f"    Masked Labels  : {tokenizer.decode(labels.tolist())}\n"
+                         f"    Predictions    : {tokenizer.decode(preds.tolist())}\n")
+        return "".join(lines)
 
 
 class _KHotCrossEntropyFn(torch.autograd.Function):

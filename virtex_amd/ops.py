@@ -841,6 +841,49 @@ def tied_ce_bwd(hidden, weight, bias, targets, lse, lc, grad_out, ignore_index=0
     return d
 
 
+# ---------------------------------------------------------------------------------------
+# masked language modelling: the labelled rows only (csrc/masked_ce.hip)
+def label_compact(labels, ignore_index, V):
+    """labels int64 [R] -> (rows int32 [R]: the labelled rows ascending, valid up to count; slot int32 [R]: position of
+    every row in that list or -1; count int32 [1]).  Labelled: label != ignore_index and 0 <= label < V."""
+    _chk(labels, "labels", torch.int64)
+    assert labels.dim() == 1
+    R = labels.numel()
+    rows, slot = (torch.empty(R, dtype=torch.int32, device=labels.device) for _ in range(2))
+    count = torch.empty(1, dtype=torch.int32, device=labels.device)
+    call("vtx_label_compact", ptr(labels), c_int(ignore_index), c_int(V), ptr(rows), ptr(slot), ptr(count), c_int(R),
+         stream_ptr(labels))
+    return rows, slot, count
+
+
+def rows_pack(hidden, labels, rows, count, cap, ignore_index=0):
+    """hidden [R,H] (row stride >= H) -> (packed [cap,H], packed_targets int64 [cap]): row i < min(count, cap) is
+    hidden[rows[i]] with its label, the rest zeros with target ignore_index; count > cap poisons packed row 0 with NaN."""
+    assert hidden.dim() == 2 and hidden.stride(1) == 1
+    R, H = hidden.shape
+    _chk(labels, "labels", torch.int64); _chk(rows, "rows", torch.int32); _chk(count, "count", torch.int32)
+    if labels.numel() != R or rows.numel() != R or count.numel() != 1:
+        raise _lib.VtxError(f"rows_pack: labels / rows must have the {R} rows of hidden, count one element")
+    packed = torch.empty(cap, H, dtype=hidden.dtype, device=hidden.device)
+    targets = torch.empty(cap, dtype=torch.int64, device=hidden.device)
+    call("vtx_rows_pack", c_int(dtype_code(hidden.dtype)), ptr(hidden), c_long(hidden.stride(0)), ptr(labels), ptr(rows), ptr(count),
+         c_int(cap), ptr(packed), ptr(targets), c_int(ignore_index), c_int(H), stream_ptr(hidden))
+    return packed, targets
+
+
+def rows_unpack(dpacked, slot, out=None):
+    """dfull [R,H] = dpacked[slot[r]] where 0 <= slot[r] < cap, zeros elsewhere (out: a [R,H] view, row stride >= H)."""
+    _chk(dpacked, "dpacked"); _chk(slot, "slot", torch.int32)
+    cap, H = dpacked.shape
+    R = slot.numel()
+    if out is None:
+        out = torch.empty(R, H, dtype=dpacked.dtype, device=dpacked.device)
+    assert out.shape == (R, H) and out.stride(1) == 1 and out.dtype == dpacked.dtype
+    call("vtx_rows_unpack", c_int(dtype_code(dpacked.dtype)), ptr(dpacked), ptr(slot), c_int(cap), ptr(out), c_long(out.stride(0)),
+         c_int(R), c_int(H), stream_ptr(dpacked))
+    return out
+
+
 def beam_step(logits, last, score_in, images, per_node, beam, eos):
     """One beam-search step on the device (vtx_beam_step).  logits fp32 [rows, V]; last int64 [rows] or None (first
     step); score_in fp32 [rows] or None.  Returns (score [images, beam], parent [images, beam], token [images, beam])."""
