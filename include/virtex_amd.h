@@ -190,6 +190,33 @@ int vtx_jpeg_entropy_decode(const void* data, long nbytes, short* coef, long coe
 int vtx_jpeg_reconstruct(const void* data, long nbytes, const short* coef_dev, const unsigned short* qt_dev,
                          unsigned char* planes_dev, unsigned char* rgb_dev, int apply_orientation, void* stream);
 
+/* ---- JPEG entropy decoding on the device (csrc/jpeg_entropy.hip) ----------
+ * The alternative to vtx_jpeg_entropy_decode: a self-synchronising parallel Huffman decoder (one lane per subsequence of
+ * `subseq_bits` bits, a multiple of 32 and >= 128) that leaves the SAME int16 coefficients in device memory, for a whole chunk
+ * of images per call.  The host only parses markers and scans bytes for the extent of the restart intervals:
+ *   vtx_jpeg_describe        same streams, same refusals and codes as vtx_jpeg_info.  dinfo[8] = {descriptor bytes, scan bytes,
+ *                            subsequences, workgroups, restart intervals, coefficient blocks, lanes per workgroup, offset of the
+ *                            quantisation tables (uint16 [4][64], for vtx_jpeg_reconstruct) inside the descriptor}.
+ *                            desc == NULL: sizes only.  Otherwise writes the image's descriptor (geometry, packed Huffman
+ *                            tables, segment table; csrc/jpeg_entropy.h) to `desc` and copies its scan bytes to `scan_out`;
+ *                            place[4] = {offset of scan_out in the chunk buffer, first workgroup, first int16 of the image in the
+ *                            coefficient buffer, status slot}.  Descriptors start on 16-byte boundaries of the chunk buffer.
+ *   vtx_jpeg_entropy_decode_device
+ *                            chunk_dev: the chunk buffer on the device, holding besides descriptors and scan bytes
+ *                            int[n_wg] at wg_table_off (per workgroup the offset of its image's descriptor) and int[n_images]
+ *                            at img_table_off (per image the same); max_wg: workgroups of the largest image; coef_dev: zeroed
+ *                            and filled here, [component][block row][block column][64] per image at its offset; status_dev:
+ *                            2 ints per image, {0 or VTX_ERR_ARG, reason: 1 invalid code, 2 DC category > 11, 3 AC run past
+ *                            63, 4 coefficient count does not match the frame}; work_dev: (4 * 256 + 2) * n_wg + 4 ints of
+ *                            scratch whose last four count the lanes final after 1 / 2 / more decodes and the decodes of the
+ *                            passes across workgroups.  Nothing is read back; a bad stream sets its status and costs no more
+ *                            time than a good one (a missing restart marker is refused by vtx_jpeg_describe). */
+int vtx_jpeg_describe(const void* data, long nbytes, int subseq_bits, int* dinfo, void* desc, long desc_cap,
+                      void* scan_out, long scan_cap, const long* place);
+int vtx_jpeg_entropy_decode_device(const void* chunk_dev, long wg_table_off, long img_table_off, int n_images, int n_wg,
+                                   int max_wg, short* coef_dev, long coef_elems, int* status_dev, int* work_dev,
+                                   long work_ints, void* stream);
+
 /* ---- per-launch timing of the contraction kernels (bench.py roofline leg) ----------------
  * Between vtx_profile_start() and vtx_profile_stop() every contraction-kernel launch carries a start and a stop
  * HIP event (hipExtLaunchKernel: the dispatch's own begin / end timestamps, i.e. what rocprofv3 reports).  stop() synchronises the device and returns the number of kernel classes

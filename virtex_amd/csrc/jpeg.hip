@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "vtx_common.h"
+#include "jpeg_entropy.h"
 
 namespace {
 
@@ -484,5 +485,92 @@ extern "C" int vtx_jpeg_reconstruct(const void* data, long nbytes, const short* 
     ca.outW = swap ? P.H : P.W; ca.outH = swap ? P.W : P.H;
     hipLaunchKernelGGL(jpeg_color_kernel, dim3(vtx_cdiv((long)P.W * P.H, 256)), dim3(256), 0, st, planes_dev, rgb_dev, ca);
     VTX_LAUNCH_CHECK();
+    return VTX_OK;
+}
+
+// ---- the host half of the device entropy decoder (jpeg_entropy.hip) ----------------------------------------------------
+// Markers, tables and a BYTE scan for the extent of every restart interval: no bit of the entropy-coded data is decoded here.
+// dinfo[8] = {descriptor bytes, scan bytes, subsequences, workgroups, segments, coefficient blocks, lanes per workgroup, offset of
+// the four quantisation tables (uint16 [4][64], what vtx_jpeg_reconstruct reads) inside the descriptor}.
+// desc == NULL: sizes only.  Otherwise the descriptor (VtxJpegDesc + packed Huffman tables + segment table) is written to
+// `desc` and the scan's bytes are copied to `scan_out`; place[4] = {offset of scan_out inside the chunk buffer, first workgroup,
+// first int16 of the image in the coefficient buffer, status slot} is where the caller put the image in its chunk.
+extern "C" int vtx_jpeg_describe(const void* data, long nbytes, int subseq_bits, int* dinfo, void* desc, long desc_cap,
+                                 void* scan_out, long scan_cap, const long* place) {
+    VTX_CHECK(data && dinfo && nbytes > 0, VTX_ERR_ARG, "jpeg_describe: null pointer");
+    VTX_CHECK(subseq_bits >= 128 && subseq_bits % 32 == 0 && subseq_bits <= (1 << 20), VTX_ERR_ARG,
+              "jpeg_describe: subseq_bits = %d (a multiple of 32, 128 at least)", subseq_bits);
+    VTX_CHECK(!desc || (scan_out && place), VTX_ERR_ARG, "jpeg_describe: descriptor without scan buffer / placement");
+    const unsigned char* d = (const unsigned char*)data;
+    Parsed P;
+    const int rc = parse(d, nbytes, P);
+    if (rc) return rc;
+    const long scan0 = P.scan - d, sb = subseq_bits / 8;
+    const long total_mcus = (long)P.mcux * P.mcuy, seg_mcus = P.restart ? P.restart : total_mcus;
+    const long nseg = (total_mcus + seg_mcus - 1) / seg_mcus;
+    // packed tables: one per distinct (class, index) the scan's components name
+    int ntab = 0, dc_tab[3] = {0, 0, 0}, ac_tab[3] = {0, 0, 0};
+    const Huff* tabs[VTX_JPEG_MAX_TABLES];
+    for (int k = 0; k < P.ncomp; ++k) {
+        const Huff* want[2] = {&P.dc[P.c[k].td], &P.ac[P.c[k].ta]};
+        for (int w = 0; w < 2; ++w) {
+            int t = 0;
+            while (t < ntab && tabs[t] != want[w]) ++t;
+            if (t == ntab) tabs[ntab++] = want[w];
+            (w ? ac_tab : dc_tab)[k] = t;
+        }
+    }
+    const long tab_off = sizeof(VtxJpegDesc), seg_off = tab_off + (long)ntab * sizeof(VtxJpegTable);
+    const long qt_off = (seg_off + (nseg + 1) * (long)sizeof(VtxJpegSegment) + 15) / 16 * 16, desc_bytes = qt_off + (long)sizeof(P.qt);
+    VTX_CHECK(desc_bytes < (1l << 30) && nbytes < (1l << 31), VTX_ERR_SHAPE, "jpeg_describe: %ld restart intervals / %ld bytes are not taken", nseg, nbytes);
+    VTX_CHECK(!desc || desc_cap >= desc_bytes, VTX_ERR_WORKSPACE, "jpeg_describe: descriptor buffer holds %ld bytes, %ld needed", desc_cap, desc_bytes);
+    VtxJpegSegment* segs = desc ? (VtxJpegSegment*)((char*)desc + seg_off) : nullptr;
+    long q = scan0, nsub = 0;
+    for (long s = 0; s < nseg; ++s) {
+        if (s > 0) {                                                                // the next RSTn, as decode_scan looks for it
+            while (q + 1 < nbytes && !(d[q] == 0xFF && d[q + 1] >= 0xD0 && d[q + 1] <= 0xD7)) ++q;
+            if (q + 1 >= nbytes) { vtx_set_error("jpeg: restart marker missing"); return VTX_ERR_ARG; }
+            q += 2;
+        }
+        const long begin = q;
+        while (q < nbytes) {                                                        // up to the first marker: FF not followed by 00
+            if (d[q] != 0xFF) { ++q; continue; }
+            if (q + 1 < nbytes && d[q + 1] == 0x00) q += 2; else break;
+        }
+        if (segs) segs[s] = VtxJpegSegment{(int)(begin - scan0), (int)(q - scan0), (int)nsub};
+        nsub += (q - begin + sb - 1) / sb;
+    }
+    const long scan_bytes = q - scan0, nwg = nsub ? (nsub + VTX_JPEG_WG - 1) / VTX_JPEG_WG : 1;
+    dinfo[0] = (int)desc_bytes; dinfo[1] = (int)scan_bytes; dinfo[2] = (int)nsub; dinfo[3] = (int)nwg; dinfo[4] = (int)nseg;
+    dinfo[5] = (int)P.total_blocks; dinfo[6] = VTX_JPEG_WG; dinfo[7] = (int)qt_off;
+    if (!desc) return VTX_OK;
+    VTX_CHECK(scan_cap >= scan_bytes, VTX_ERR_WORKSPACE, "jpeg_describe: scan buffer holds %ld bytes, %ld needed", scan_cap, scan_bytes);
+    VTX_CHECK(place[0] >= 0 && place[0] + scan_bytes < (1l << 31) && place[1] >= 0 && place[2] >= 0 && place[3] >= 0, VTX_ERR_ARG, "jpeg_describe: placement out of range");
+    segs[nseg] = VtxJpegSegment{(int)scan_bytes, (int)scan_bytes, (int)nsub};
+    memcpy(scan_out, d + scan0, (size_t)scan_bytes);
+    VtxJpegDesc D;
+    memset(&D, 0, sizeof(D));
+    D.desc_bytes = (int)desc_bytes; D.byte_off = (int)place[0]; D.nbytes = (int)scan_bytes;
+    D.nsub = (int)nsub; D.nseg = (int)nseg; D.first_wg = (int)place[1]; D.nwg = (int)nwg; D.subseq_bytes = (int)sb;
+    D.seg_mcus = (int)seg_mcus; D.total_mcus = (int)total_mcus; D.mcux = P.mcux;
+    D.ncomp = P.ncomp; D.total_blocks = (int)P.total_blocks;
+    D.coef_off_lo = (int)(place[2] & 0xffffffffl); D.coef_off_hi = (int)(place[2] >> 32); D.status_slot = (int)place[3];
+    int b = 0;
+    for (int k = 0; k < P.ncomp; ++k) {
+        D.comp_off[k] = (int)P.c[k].off; D.comp_bw[k] = P.c[k].bw; D.comp_h[k] = P.c[k].h; D.comp_v[k] = P.c[k].v;
+        D.dc_tab[k] = dc_tab[k]; D.ac_tab[k] = ac_tab[k];
+        for (int v = 0; v < P.c[k].v; ++v)
+            for (int h = 0; h < P.c[k].h; ++h, ++b) { D.blk_comp[b] = k; D.blk_h[b] = h; D.blk_v[b] = v; }
+    }
+    D.bpm = b; D.ntab = ntab; D.tab_off = (int)tab_off; D.seg_off = (int)seg_off; D.qt_off = (int)qt_off;
+    memcpy(desc, &D, sizeof(D));
+    memcpy((char*)desc + qt_off, P.qt, sizeof(P.qt));
+    for (int t = 0; t < ntab; ++t) {
+        VtxJpegTable T;
+        memcpy(T.look, tabs[t]->look, sizeof(T.look));
+        for (int l = 0; l <= 16; ++l) { T.maxcode[l] = l ? tabs[t]->maxcode[l] : -1; T.valptr[l] = l ? tabs[t]->valptr[l] : 0; }
+        memcpy(T.vals, tabs[t]->vals, sizeof(T.vals));
+        memcpy((char*)desc + tab_off + (long)t * sizeof(VtxJpegTable), &T, sizeof(T));
+    }
     return VTX_OK;
 }

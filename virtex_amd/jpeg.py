@@ -7,7 +7,12 @@ annotation bookkeeping of `CocoCaptionsDataset.__init__` (:22-52).
 the int16 coefficients.  Host: marker parsing + Huffman decoding (C++, thread-safe, releases the GIL); device: dequantise,
 inverse DCT, chroma upsampling, colour conversion -- bit-exact with libjpeg-turbo's defaults (csrc/jpeg.hip; pinned against
 Pillow's libjpeg-turbo in tests/test_jpeg.py, CPU restatement in oracle/jpeg.py).  There is no fallback decoder: a stream the
-kernels do not take (progressive, CMYK, ...) raises VtxError -- convert such files once, offline."""
+kernels do not take (progressive, CMYK, ...) raises VtxError -- convert such files once, offline.
+
+`entropy="device"` moves the Huffman decoding onto the device as well (csrc/jpeg_entropy.hip: a self-synchronising parallel
+decoder, one lane per `subseq_bits` bits of the scan): the host parses markers, the file's scan bytes and a small descriptor
+cross PCIe, and no coefficient ever exists in host memory.  The coefficients are the host decoder's, bit for bit.  The default
+stays `"host"`."""
 import ctypes
 import json
 import os
@@ -31,9 +36,105 @@ def jpeg_info(data: bytes) -> Dict[str, int]:
     return dict(zip(keys, [int(v) for v in info]))
 
 
-def decode_jpeg(data: bytes, device, apply_orientation: bool = True) -> torch.Tensor:
-    """bytes of one baseline JPEG -> uint8 (H, W, 3) RGB on `device` (EXIF orientation applied like cv2.imread)."""
+SUBSEQ_BITS = 512       # default subsequence length of the device entropy decoder (256 / 512 / 1 024 / 2 048 swept)
+_STATUS_REASON = {1: "corrupt Huffman code", 2: "corrupt DC code", 3: "corrupt AC run", 4: "coefficient count does not match the frame"}
+
+
+def _check_entropy(entropy: str):
+    if entropy not in ("host", "device"):
+        raise ValueError(f"entropy must be 'host' or 'device', not {entropy!r}")
+
+
+def _describe(data: bytes, subseq_bits: int):
+    dinfo = (ctypes.c_int * 8)()
+    _lib.call("vtx_jpeg_describe", ctypes.c_char_p(data), c_long(len(data)), c_int(subseq_bits), dinfo, None, c_long(0), None,
+              c_long(0), None)
+    return [int(v) for v in dinfo]
+
+
+def _align(n: int, a: int = 16) -> int:
+    return (n + a - 1) // a * a
+
+
+def entropy_decode_device(blobs, device, subseq_bits: int = SUBSEQ_BITS, pool=None, host=None):
+    """Huffman-decode a chunk of streams on the device in ONE launch sequence.  Returns (coef, coef_offs, chunk, qt_offs, status,
+    work): the int16 coefficients of all images in one device tensor with each image's first element, the chunk buffer on the
+    device (descriptors, scan bytes) with the byte offset of every image's quantisation tables, the status pairs (still on the
+    device: nothing is read back here) and the scratch whose last four ints are the synchronisation counters.  `host`: a pinned
+    uint8 staging tensor to reuse; `pool`: an executor for the per-image marker parsing."""
     device = torch.device(device)
+    n = len(blobs)
+    run = (lambda f, it: list(pool.map(f, it))) if pool is not None else (lambda f, it: [f(i) for i in it])
+    dinfos = run(lambda i: _describe(blobs[i], subseq_bits), range(n))
+    n_wg = sum(d[3] for d in dinfos)
+    pos = _align(4 * n_wg)                                                # int wg_desc[n_wg], int img_desc[n]
+    img_table_off, pos = pos, _align(pos + 4 * n)
+    desc_offs, scan_offs, coef_offs, first_wg, wg, co = [], [], [], [], 0, 0
+    for d in dinfos:
+        desc_offs.append(pos); pos = _align(pos + d[0])
+    for d in dinfos:
+        scan_offs.append(pos); pos = _align(pos + d[1])
+        first_wg.append(wg); wg += d[3]
+        coef_offs.append(co); co += d[5] * 64                             # (64 int16 per block: 128-byte slices)
+    if host is None or host.numel() < pos:
+        host = torch.empty(pos, dtype=torch.uint8, pin_memory=(device.type == "cuda"))
+    tables = host[:img_table_off + 4 * n].view(torch.int32)
+    tables[:n_wg] = torch.repeat_interleave(torch.tensor(desc_offs, dtype=torch.int32), torch.tensor([d[3] for d in dinfos]))
+    tables[img_table_off // 4:] = torch.tensor(desc_offs, dtype=torch.int32)
+    base = host.data_ptr()
+
+    def fill(i):
+        place = (c_long * 4)(scan_offs[i], first_wg[i], coef_offs[i], i)
+        _lib.call("vtx_jpeg_describe", ctypes.c_char_p(blobs[i]), c_long(len(blobs[i])), c_int(subseq_bits), (ctypes.c_int * 8)(),
+                  ctypes.c_void_p(base + desc_offs[i]), c_long(dinfos[i][0]), ctypes.c_void_p(base + scan_offs[i]),
+                  c_long(dinfos[i][1]), place)
+
+    run(fill, range(n))
+    chunk = torch.empty(pos, dtype=torch.uint8, device=device)
+    chunk.copy_(host[:pos], non_blocking=True)                            # the ONE copy of the chunk: file bytes + descriptors
+    coef = torch.empty(max(co, 8), dtype=torch.int16, device=device)
+    status = torch.empty(2 * n, dtype=torch.int32, device=device)
+    work = torch.empty((4 * dinfos[0][6] + 2) * n_wg + 4, dtype=torch.int32, device=device)
+    _lib.call("vtx_jpeg_entropy_decode_device", ptr(chunk), c_long(0), c_long(img_table_off), c_int(n), c_int(n_wg),
+              c_int(max(d[3] for d in dinfos)), ptr(coef), c_long(coef.numel()), ptr(status), ptr(work), c_long(work.numel()),
+              stream_ptr(coef))
+    return coef, coef_offs, chunk, [desc_offs[i] + dinfos[i][7] for i in range(n)], status, work
+
+
+def _raise_failed(status: torch.Tensor, first_index: int = 0):
+    """the chunk's status pairs, read back once: VtxError naming the first failed image"""
+    st = status.cpu().view(-1, 2)
+    bad = torch.nonzero(st[:, 0]).flatten()
+    if bad.numel():
+        i = int(bad[0])
+        raise _lib.VtxError(f"vtx_jpeg_entropy_decode_device failed ({int(st[i, 0])}): jpeg: image {first_index + i}: "
+                            f"{_STATUS_REASON.get(int(st[i, 1]), 'corrupt scan')}")
+
+
+def _reconstruct_chunk(blobs, infos, coef, coef_offs, chunk, qt_offs, planes, apply_orientation, device):
+    out = []
+    for i, (data, info) in enumerate(zip(blobs, infos)):
+        swap = apply_orientation and info["orientation"] >= 5
+        H, W = (info["width"], info["height"]) if swap else (info["height"], info["width"])
+        rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=device)
+        _lib.call("vtx_jpeg_reconstruct", ctypes.c_char_p(data), c_long(len(data)), ptr(coef[coef_offs[i]:]),
+                  ptr(chunk[qt_offs[i]:]), ptr(planes), ptr(rgb), c_int(1 if apply_orientation else 0), stream_ptr(rgb))
+        out.append(rgb)
+    return out
+
+
+def decode_jpeg(data: bytes, device, apply_orientation: bool = True, entropy: str = "host", subseq_bits: int = SUBSEQ_BITS) -> torch.Tensor:
+    """bytes of one baseline JPEG -> uint8 (H, W, 3) RGB on `device` (EXIF orientation applied like cv2.imread).
+    entropy: where the Huffman decoding runs, "host" (default) or "device"."""
+    _check_entropy(entropy)
+    device = torch.device(device)
+    if entropy == "device":
+        info = jpeg_info(data)
+        coef, coef_offs, chunk, qt_offs, status, _ = entropy_decode_device([data], device, subseq_bits)
+        planes = torch.empty(info["plane_bytes"], dtype=torch.uint8, device=device)
+        rgb = _reconstruct_chunk([data], [info], coef, coef_offs, chunk, qt_offs, planes, apply_orientation, device)[0]
+        _raise_failed(status)
+        return rgb
     info = jpeg_info(data)
     pin = device.type == "cuda"
     coef = torch.empty(info["blocks"] * 64, dtype=torch.int16, pin_memory=pin)
@@ -66,19 +167,47 @@ def _staging_area(device, n16: int):
     return ent
 
 
-def decode_jpeg_batch(blobs, device, threads: int = 8, apply_orientation: bool = True, chunk: int = 16) -> List[torch.Tensor]:
+def decode_jpeg_batch(blobs, device, threads: int = 8, apply_orientation: bool = True, chunk: int = 16, entropy: str = "host",
+                      subseq_bits: int = SUBSEQ_BITS) -> List[torch.Tensor]:
     """Many files at once.  The serial Huffman decoding of the images runs on `threads` host threads (the C entry points hold no
     Python state and ctypes releases the GIL), each writing its int16 coefficients into ITS slice of one page-locked staging
     buffer; the main thread follows in input order: as soon as the next `chunk` images are decoded, their slice crosses PCIe in ONE
     asynchronous copy and the per-image device work (inverse DCT, upsampling, colour conversion: two launches per image, all
     images sharing one plane scratch in stream order) is enqueued on the caller's stream.  Per image the main thread issues one C
     call and one small allocation (round 5 allocated page-locked memory and issued two copies per image: 7 400-9 900 images/s
-    whatever the thread count; this form scales with the host threads).  Returns the uint8 (H, W, 3) tensors in input order."""
+    whatever the thread count; this form scales with the host threads).  Returns the uint8 (H, W, 3) tensors in input order.
+    entropy="device": per chunk the host threads only parse markers; the chunk's scan bytes and descriptors cross PCIe in one
+    copy, ONE call Huffman-decodes the chunk on the device, the per-image reconstruct launches read the device coefficients, and
+    the chunk's status words are read back once behind them (VtxError names the first failed image)."""
+    _check_entropy(entropy)
     device = torch.device(device)
     if len(blobs) == 0:
         return []
     with _staging_lock:
+        if entropy == "device":
+            return _decode_jpeg_batch_device(blobs, device, threads, apply_orientation, chunk, subseq_bits)
         return _decode_jpeg_batch(blobs, device, threads, apply_orientation, chunk)
+
+
+def _decode_jpeg_batch_device(blobs, device, threads, apply_orientation, chunk, subseq_bits):
+    from concurrent.futures import ThreadPoolExecutor
+    n = len(blobs)
+    out = []
+    with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
+        infos = list(pool.map(jpeg_info, blobs))
+        planes = torch.empty(max(i["plane_bytes"] for i in infos), dtype=torch.uint8, device=device)
+        for c0 in range(0, n, chunk):
+            c1 = min(n, c0 + chunk)
+            stage = _staging_area(device, 1 << 20)                        # (waits for the previous chunk's copy out of it)
+            coef, coef_offs, chunk_d, qt_offs, status, _ = entropy_decode_device(blobs[c0:c1], device, subseq_bits, pool,
+                                                                                 stage[0].view(torch.uint8))   # (a chunk it cannot hold stages in a buffer of its own)
+            if device.type == "cuda":
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(device))
+                stage[1] = ev
+            out += _reconstruct_chunk(blobs[c0:c1], infos[c0:c1], coef, coef_offs, chunk_d, qt_offs, planes, apply_orientation, device)
+            _raise_failed(status, c0)
+    return out
 
 
 def _decode_jpeg_batch(blobs, device, threads, apply_orientation, chunk):
@@ -139,7 +268,9 @@ class CocoCaptionsReader:
     order (annotation order of first appearance), same caption normalisation.  `read_bytes(idx)` / `instances` give the raw
     pieces to loaders that decode a whole batch from a thread pool."""
 
-    def __init__(self, data_root: str, split: str, device="cuda"):
+    def __init__(self, data_root: str, split: str, device="cuda", entropy: str = "host"):
+        _check_entropy(entropy)
+        self.entropy = entropy
         image_dir = os.path.join(data_root, f"{split}2017")
         with open(os.path.join(data_root, "annotations", f"captions_{split}2017.json")) as fh:
             captions = json.load(fh)
@@ -159,4 +290,4 @@ class CocoCaptionsReader:
 
     def __getitem__(self, idx: int):
         image_id, _, captions = self.instances[idx]
-        return {"image_id": image_id, "image": decode_jpeg(self.read_bytes(idx), self.device), "captions": captions}
+        return {"image_id": image_id, "image": decode_jpeg(self.read_bytes(idx), self.device, entropy=self.entropy), "captions": captions}
