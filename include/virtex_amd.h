@@ -475,6 +475,20 @@ int vtx_beam_step(const float* logits, long ld, const long long* last, const flo
                   int V, int eos, int per_node, int beam, float* cand_lp, long long* cand_tok, float* score_out,
                   long long* parent_out, long long* token_out, void* stream);
 
+/* ---- one nucleus-sampling (top-p) step on the device (csrc/nucleus.hip) -------------------
+ * Replaces the aten::sort / softmax / cumsum / scatter_ / masked_fill_ / softmax / multinomial chain of
+ * virtex/utils/nucleus_sampling.py:78-113 (opt-in: AutoRegressiveNucleusSampling(draw="device")).  logits:[rows][V] fp32 (row
+ * stride ld); last:[rows] int64 previous tokens; u:[rows] fp32 uniforms in [0, 1) drawn by the caller; 0 < p < 1 (taken to 24
+ * fractional bits).  Per row, with the integer masses w_i = rint(exp(x_i - max x) * 2^40) and Z their sum:
+ *   order: descending logit, ties by ascending token index;  nucleus: the token at rank i is kept iff i == 0 or the mass of
+ *   the ranks before it is <= p Z (the crossing token is kept), kept_out[r] = their number;  candidates: the kept tokens
+ *   except last[r];  draw: with M the candidates' mass and t = floor(floor(u 2^24) M / 2^24), the first candidate in rank
+ *   order whose inclusive cumulative mass exceeds t;  no candidates (last[r] alone is the nucleus: the reference's softmax
+ *   over logits that are all -1e12 is uniform): min(floor(u V), V - 1);  last[r] == eos: eos (kept_out is still written).
+ * Integer sums: the same inputs give the same bits on every run.  V <= 2^22, else VTX_ERR_SHAPE. */
+int vtx_nucleus_step(const float* logits, long ld, const long long* last, const float* u, int rows, int V, int eos, float p,
+                     long long* token_out, int* kept_out, void* stream);
+
 /* ---- small helpers -------------------------------------------------------------------- */
 long vtx_colsum_workspace_floats(int C);
 int vtx_colsum_acc(int dtype, const void* x, long ld, float* out /*[C] +=*/, float* workspace, int R, int C,

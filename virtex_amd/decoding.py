@@ -10,7 +10,8 @@ text head on the whole prefix (the reference has no KV cache, captioning.py:165-
 Everything here is batched -- no per-row Python loops (the reference walks the batch x beam rows in Python at
 beam_search.py:156-157 and nucleus_sampling.py:95-101).  When the logits live where the HIP library runs, a beam-search
 step is ONE C-ABI call (`vtx_beam_step`: log-softmax, repetition penalty, finished-beam rule, per-beam and per-image
-top-k on the device); on plain CPU tensors the same arithmetic runs as torch tensor operations.  `IncrementalDecodingStep`
+top-k on the device), and so is a nucleus-sampling step built with draw="device" (`vtx_nucleus_step`: a weighted radix select
+for the cut and for the draw, no sort); on plain CPU tensors the same arithmetic runs as torch tensor operations.  `IncrementalDecodingStep`
 (below) is the KV-cached step function the models hand to these decoders.
 """
 import warnings
@@ -111,15 +112,21 @@ def _hip_available(t: torch.Tensor) -> bool:
 
 
 class AutoRegressiveNucleusSampling:
-    def __init__(self, eos_index: int, max_steps: int = 50, nucleus_size: float = 0.9):
+    def __init__(self, eos_index: int, max_steps: int = 50, nucleus_size: float = 0.9, draw: str = "torch"):
+        if draw not in ("torch", "device"):
+            raise ValueError(f"draw must be 'torch' or 'device', got {draw!r}")
         self._eos_index = eos_index
         self.max_steps = max_steps
         self.nucleus_size = nucleus_size
+        self.draw = draw
 
     @torch.no_grad()
     def search(self, start_predictions: torch.Tensor, step: Callable[..., torch.Tensor]) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-        """-> (sampled tokens (B, <= max_steps), None).  Draws come from ``torch.multinomial`` on the device's
-        default generator, one call per step with the same probabilities as the reference computes."""
+        """-> (sampled tokens (B, <= max_steps), None).  draw="torch": draws come from ``torch.multinomial`` on the device's
+        default generator, one call per step with the same probabilities as the reference computes.  draw="device" (where
+        the HIP library runs): a step's whole selection is one `vtx_nucleus_step` call (csrc/nucleus.hip) fed one
+        ``torch.rand(B)`` from the default generator -- the same distribution, reproducible under ``torch.manual_seed``,
+        but not ``multinomial``'s random stream, hence opt-in."""
         B, eos = start_predictions.size(0), self._eos_index
         seq = start_predictions.view(B, 1)
         for _ in range(self.max_steps):
@@ -127,6 +134,12 @@ class AutoRegressiveNucleusSampling:
             if bool((last == eos).all()):
                 break
             logits = step(seq)                                                 # (B, V); filtered in place like the reference
+            if self.draw == "device" and _hip_available(logits):
+                from . import ops
+                u = torch.rand(B, device=logits.device, dtype=torch.float32)
+                nxt, _ = ops.nucleus_step(logits.float().contiguous(), last.contiguous(), u, eos, self.nucleus_size)
+                seq = torch.cat([seq, nxt.unsqueeze(1)], dim=1)
+                continue
             ordered, order = torch.sort(logits, descending=True)
             mass = torch.cumsum(torch.softmax(ordered, dim=-1), dim=-1)
             outside = mass > self.nucleus_size

@@ -113,6 +113,7 @@ class CaptionDecoderFactory(Factory):
             kwargs["beam_size"] = _C.MODEL.DECODER.BEAM_SIZE
         elif _C.MODEL.DECODER.NAME == "nucleus_sampling":
             kwargs["nucleus_size"] = _C.MODEL.DECODER.NUCLEUS_SIZE
+            kwargs["draw"] = getattr(_C.MODEL.DECODER, "DRAW", "torch")   # "device": vtx_nucleus_step (not a reference key)
         return cls.create(_C.MODEL.DECODER.NAME, **kwargs)
 
 

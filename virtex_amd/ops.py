@@ -902,6 +902,19 @@ def beam_step(logits, last, score_in, images, per_node, beam, eos):
     return score, parent, token
 
 
+def nucleus_step(logits, last, u, eos, p):
+    """One nucleus-sampling step on the device (vtx_nucleus_step).  logits fp32 [rows, V]; last int64 [rows]; u fp32 [rows]
+    uniforms in [0, 1).  Returns (token int64 [rows], kept int32 [rows]: the size of every row's nucleus)."""
+    rows, V = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and last.numel() == rows and u.numel() == rows
+    _chk(last, "last", torch.int64); _chk(u, "u", torch.float32)
+    token = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    kept = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    call("vtx_nucleus_step", ptr(logits), c_long(logits.stride(0)), ptr(last), ptr(u), c_int(rows), c_int(V), c_int(eos),
+         c_float(p), ptr(token), ptr(kept), stream_ptr(logits))
+    return token, kept
+
+
 _colsum_ws = {}
 
 
