@@ -41,6 +41,60 @@ def test_no_cpu_fallback_in_product_build():
         _lib.use_library("/nonexistent/libvirtex_amd.so")
 
 
+def _header_parameter_counts():
+    """{entry point: number of parameters}, counted from the comment-stripped header by splitting each parameter list."""
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "virtex_amd.h")).read(), flags=re.S)
+    decls = re.findall(r"\b(vtx_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header)
+    return {name: 0 if params.strip() == "void" else len(params.split(",")) for name, params in decls}
+
+
+def _load(which):
+    if which == "emu":
+        from backends import select
+        select("emu")
+    else:
+        _lib.use_library(build.build_hip())          # loads without a device
+    return _lib.lib()
+
+
+@pytest.mark.parametrize("which", ["emu", "hip"])
+def test_signatures_are_bound_from_the_header(which):
+    lib = _load(which)
+    counts = _header_parameter_counts()
+    assert sorted(counts) == _header_symbols()
+    assert {s: len(getattr(lib, s).argtypes) for s in counts} == counts
+    longs = ("vtx_layernorm_workspace_floats", "vtx_bn_workspace_floats", "vtx_tied_ce_partial_floats", "vtx_colsum_workspace_floats")
+    for s in counts:
+        want = ctypes.c_long if s in longs else ctypes.c_char_p if s in ("vtx_backend", "vtx_last_error") else ctypes.c_int
+        assert getattr(lib, s).restype is want, s
+    assert lib.vtx_add.argtypes == (ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p)
+    assert lib.vtx_set_switch.argtypes == (ctypes.c_char_p, ctypes.c_int)
+    assert lib.vtx_dropout_bwd.argtypes[4:6] == (ctypes.c_float, ctypes.c_uint64)
+
+
+@pytest.mark.parametrize("which", ["emu", "hip"])
+def test_a_call_that_disagrees_with_the_header_raises_before_the_launch(which):
+    """The pointers are NULL: vtx_add would refuse them with VTX_ERR_ARG if one of these calls got through, and the message
+    would be the library's, not the binding's."""
+    _load(which)
+    good = (0, None, None, None, 16, None)
+    with pytest.raises(_lib.VtxError, match=r"vtx_add takes 6 arguments.*5 given"):
+        _lib.call("vtx_add", *good[:-1])
+    with pytest.raises(_lib.VtxError, match=r"vtx_add takes 6 arguments.*7 given"):
+        _lib.call("vtx_add", *good, None)
+    with pytest.raises(_lib.VtxError, match=r"vtx_add: argument 1:"):
+        _lib.call("vtx_add", 0.0, *good[1:])                        # a Python float in an int slot
+    with pytest.raises(_lib.VtxError, match=r"vtx_add: argument 1:"):
+        _lib.call("vtx_add", ctypes.c_long(0), *good[1:])           # a wrapper of another type than the header's
+
+
+def test_header_parser_refuses_what_it_cannot_map():
+    with pytest.raises(_lib.VtxError, match=r"size_t n.*int vtx_new_thing\(int dtype, size_t n\)"):
+        _lib._parse_header("int vtx_version(void);\nint vtx_new_thing(int dtype, size_t n);\n")
+    with pytest.raises(_lib.VtxError, match=r"void vtx_new_thing\(int dtype\)"):
+        _lib._parse_header("/* a return type the ABI does not use */ void vtx_new_thing(int dtype);")
+
+
 def test_error_reporting_through_the_abi():
     from backends import select
     from virtex_amd import ops

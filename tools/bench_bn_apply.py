@@ -26,7 +26,7 @@ for (H, C) in [(112, 64), (56, 256), (56, 64), (28, 512), (28, 128), (14, 1024),
     fst = ops.BnStats(torch.rand(64 * 2 * C, device="cuda"), 64, torch.zeros(C, device="cuda"))
     rows = {"bwd fused": [], "fwd apply": [], "fwd join": []}
     for name, adj, unr, grid in VARIANTS:
-        sw("bn_adj", adj); sw("bn_grid", grid); _lib.call("vtx_set_bn_apply_unroll", _lib.c_int(unr))
+        sw("bn_adj", adj); sw("bn_grid", grid); _lib.call("vtx_set_bn_apply_unroll", ctypes.c_int(unr))
         t = timeit(lambda: ops.bn_bwd_fused(x, dz, g, mean, rstd, dg, db, st), iters=12, warm=3)
         rows["bwd fused"].append(f"{name}: {t*1e6:6.1f}us {x.numel()*6/t/1e9:5.0f}")
         t = timeit(lambda: ops.bn_fwd(x, g, beta, rm, rv, None, relu=True, stats=fst), iters=12, warm=3)
@@ -35,4 +35,4 @@ for (H, C) in [(112, 64), (56, 256), (56, 64), (28, 512), (28, 128), (14, 1024),
         rows["fwd join"].append(f"{name}: {t*1e6:6.1f}us {x.numel()*6.125/t/1e9:5.0f}")
     for k, r in rows.items():
         print(f"{k} {H:3d}x{H:<3d} C={C:<5d}| " + " | ".join(r), flush=True)
-sw("bn_adj", 1); sw("bn_grid", 8192); _lib.call("vtx_set_bn_apply_unroll", _lib.c_int(0))
+sw("bn_adj", 1); sw("bn_grid", 8192); _lib.call("vtx_set_bn_apply_unroll", ctypes.c_int(0))

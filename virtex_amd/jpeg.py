@@ -24,14 +24,12 @@ from typing import Dict, List, Tuple
 import torch
 
 from . import _lib
-from ._lib import c_int, ptr, stream_ptr
-
-c_long = ctypes.c_long
+from ._lib import ptr, stream_ptr
 
 
 def jpeg_info(data: bytes) -> Dict[str, int]:
     info = (ctypes.c_int * 8)()
-    _lib.call("vtx_jpeg_info", ctypes.c_char_p(data), c_long(len(data)), info)
+    _lib.call("vtx_jpeg_info", data, len(data), info)
     keys = ("width", "height", "components", "luma_h", "luma_v", "orientation", "blocks", "plane_bytes")
     return dict(zip(keys, [int(v) for v in info]))
 
@@ -47,8 +45,7 @@ def _check_entropy(entropy: str):
 
 def _describe(data: bytes, subseq_bits: int):
     dinfo = (ctypes.c_int * 8)()
-    _lib.call("vtx_jpeg_describe", ctypes.c_char_p(data), c_long(len(data)), c_int(subseq_bits), dinfo, None, c_long(0), None,
-              c_long(0), None)
+    _lib.call("vtx_jpeg_describe", data, len(data), subseq_bits, dinfo, None, 0, None, 0, None)
     return [int(v) for v in dinfo]
 
 
@@ -84,10 +81,9 @@ def entropy_decode_device(blobs, device, subseq_bits: int = SUBSEQ_BITS, pool=No
     base = host.data_ptr()
 
     def fill(i):
-        place = (c_long * 4)(scan_offs[i], first_wg[i], coef_offs[i], i)
-        _lib.call("vtx_jpeg_describe", ctypes.c_char_p(blobs[i]), c_long(len(blobs[i])), c_int(subseq_bits), (ctypes.c_int * 8)(),
-                  ctypes.c_void_p(base + desc_offs[i]), c_long(dinfos[i][0]), ctypes.c_void_p(base + scan_offs[i]),
-                  c_long(dinfos[i][1]), place)
+        place = (ctypes.c_long * 4)(scan_offs[i], first_wg[i], coef_offs[i], i)
+        _lib.call("vtx_jpeg_describe", blobs[i], len(blobs[i]), subseq_bits, (ctypes.c_int * 8)(), base + desc_offs[i],
+                  dinfos[i][0], base + scan_offs[i], dinfos[i][1], place)
 
     run(fill, range(n))
     chunk = torch.empty(pos, dtype=torch.uint8, device=device)
@@ -95,9 +91,8 @@ def entropy_decode_device(blobs, device, subseq_bits: int = SUBSEQ_BITS, pool=No
     coef = torch.empty(max(co, 8), dtype=torch.int16, device=device)
     status = torch.empty(2 * n, dtype=torch.int32, device=device)
     work = torch.empty((4 * dinfos[0][6] + 2) * n_wg + 4, dtype=torch.int32, device=device)
-    _lib.call("vtx_jpeg_entropy_decode_device", ptr(chunk), c_long(0), c_long(img_table_off), c_int(n), c_int(n_wg),
-              c_int(max(d[3] for d in dinfos)), ptr(coef), c_long(coef.numel()), ptr(status), ptr(work), c_long(work.numel()),
-              stream_ptr(coef))
+    _lib.call("vtx_jpeg_entropy_decode_device", ptr(chunk), 0, img_table_off, n, n_wg, max(d[3] for d in dinfos), ptr(coef),
+              coef.numel(), ptr(status), ptr(work), work.numel(), stream_ptr(coef))
     return coef, coef_offs, chunk, [desc_offs[i] + dinfos[i][7] for i in range(n)], status, work
 
 
@@ -117,8 +112,8 @@ def _reconstruct_chunk(blobs, infos, coef, coef_offs, chunk, qt_offs, planes, ap
         swap = apply_orientation and info["orientation"] >= 5
         H, W = (info["width"], info["height"]) if swap else (info["height"], info["width"])
         rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=device)
-        _lib.call("vtx_jpeg_reconstruct", ctypes.c_char_p(data), c_long(len(data)), ptr(coef[coef_offs[i]:]),
-                  ptr(chunk[qt_offs[i]:]), ptr(planes), ptr(rgb), c_int(1 if apply_orientation else 0), stream_ptr(rgb))
+        _lib.call("vtx_jpeg_reconstruct", data, len(data), ptr(coef[coef_offs[i]:]), ptr(chunk[qt_offs[i]:]), ptr(planes),
+                  ptr(rgb), 1 if apply_orientation else 0, stream_ptr(rgb))
         out.append(rgb)
     return out
 
@@ -139,16 +134,14 @@ def decode_jpeg(data: bytes, device, apply_orientation: bool = True, entropy: st
     pin = device.type == "cuda"
     coef = torch.empty(info["blocks"] * 64, dtype=torch.int16, pin_memory=pin)
     qt = torch.empty(4 * 64, dtype=torch.int16, pin_memory=pin)                 # uint16 values: same bits
-    buf = ctypes.c_char_p(data)
-    _lib.call("vtx_jpeg_entropy_decode", buf, c_long(len(data)), ctypes.c_void_p(coef.data_ptr()), c_long(coef.numel()),
-              ctypes.c_void_p(qt.data_ptr()))
+    _lib.call("vtx_jpeg_entropy_decode", data, len(data), coef.data_ptr(), coef.numel(), qt.data_ptr())
     coef_d, qt_d = coef.to(device, non_blocking=True), qt.to(device, non_blocking=True)
     planes = torch.empty(info["plane_bytes"], dtype=torch.uint8, device=device)
     swap = apply_orientation and info["orientation"] >= 5
     H, W = (info["width"], info["height"]) if swap else (info["height"], info["width"])
     rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=device)
-    _lib.call("vtx_jpeg_reconstruct", buf, c_long(len(data)), ptr(coef_d), ptr(qt_d), ptr(planes), ptr(rgb),
-              c_int(1 if apply_orientation else 0), stream_ptr(rgb))
+    _lib.call("vtx_jpeg_reconstruct", data, len(data), ptr(coef_d), ptr(qt_d), ptr(planes), ptr(rgb),
+              1 if apply_orientation else 0, stream_ptr(rgb))
     return rgb
 
 
@@ -225,8 +218,8 @@ def _decode_jpeg_batch(blobs, device, threads, apply_orientation, chunk):
 
     def work(i):
         data = blobs[i]
-        _lib.call("vtx_jpeg_entropy_decode", ctypes.c_char_p(data), c_long(len(data)), ctypes.c_void_p(base + 2 * offs[i]),
-                  c_long(infos[i]["blocks"] * 64), ctypes.c_void_p(base + 2 * (offs[i] + infos[i]["blocks"] * 64)))
+        _lib.call("vtx_jpeg_entropy_decode", data, len(data), base + 2 * offs[i], infos[i]["blocks"] * 64,
+                  base + 2 * (offs[i] + infos[i]["blocks"] * 64))
         return i
 
     dev_all = torch.empty(offs[-1], dtype=torch.int16, device=device)
@@ -245,8 +238,8 @@ def _decode_jpeg_batch(blobs, device, threads, apply_orientation, chunk):
                 H, W = (info["width"], info["height"]) if swap else (info["height"], info["width"])
                 rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=device)
                 nb = info["blocks"] * 64
-                _lib.call("vtx_jpeg_reconstruct", ctypes.c_char_p(data), c_long(len(data)), ptr(dev_all[offs[i]:offs[i] + nb]),
-                          ptr(dev_all[offs[i] + nb:offs[i] + nb + QT]), ptr(planes), ptr(rgb), c_int(1 if apply_orientation else 0),
+                _lib.call("vtx_jpeg_reconstruct", data, len(data), ptr(dev_all[offs[i]:offs[i] + nb]),
+                          ptr(dev_all[offs[i] + nb:offs[i] + nb + QT]), ptr(planes), ptr(rgb), 1 if apply_orientation else 0,
                           stream_ptr(rgb))
                 out.append(rgb)
     if device.type == "cuda":

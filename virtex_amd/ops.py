@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import c_float, c_int, c_u64, call, dtype_code, ptr, stream_ptr
+from ._lib import call, dtype_code, ptr, stream_ptr
 
 
 def _chk(t, name, dtype=None):
@@ -30,16 +30,25 @@ def layernorm_residual_fwd(x, y, gamma, beta, eps, p_drop=0.0, seed=0):
     out = torch.empty_like(x)
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    call("vtx_layernorm_residual_fwd", c_int(dtype_code(x.dtype)), ptr(x), ptr(y), ptr(gamma),
-         ptr(beta), ptr(out), ptr(mean), ptr(rstd), c_int(rows), c_int(H), c_float(eps),
-         c_float(p_drop), c_u64(seed), stream_ptr(x))
+    call("vtx_layernorm_residual_fwd", dtype_code(x.dtype), ptr(x), ptr(y), ptr(gamma), ptr(beta), ptr(out), ptr(mean), ptr(rstd),
+         rows, H, eps, p_drop, seed, stream_ptr(x))
     return out, mean, rstd
 
 
 def _ws_key(device):
     """Scratch buffers are per (device, stream): the same kernels run concurrently on the compute stream, the
     weight-gradient side stream and the shortcut-branch stream (virtex_amd/streams.py)."""
-    return (device, _lib.current_stream_handle(device) if device.type == "cuda" else 0)
+    return (device, _lib._device_stream(device))
+
+
+def _scratch(cache, device, need, floor=0, zeroed=False):
+    """The fp32 scratch buffer of `cache` for (device, current stream) when it holds `need` floats, else a new one of
+    max(need, floor) floats -- torch.zeros when `zeroed`, otherwise uninitialised -- that replaces it."""
+    key = _ws_key(device)
+    ws = cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = cache[key] = (torch.zeros if zeroed else torch.empty)(max(need, floor), dtype=torch.float32, device=device)
+    return ws
 
 
 _ln_ws = {}
@@ -52,22 +61,15 @@ def layernorm_residual_bwd(x, y, gamma, mean, rstd, dout, dgamma, dbeta, p_drop=
     _chk(x, "x"); _chk(y, "y", x.dtype); _chk(dout, "dout", x.dtype)
     dz = torch.empty_like(x)
     dy = torch.empty_like(x) if (y is not None and p_drop > 0.0) else None
-    ws = _ln_ws.get(_ws_key(x.device))
-    lib = _lib.lib()
-    lib.vtx_layernorm_workspace_floats.restype = _lib.ctypes.c_long
-    need = int(lib.vtx_layernorm_workspace_floats(c_int(H)))          # per-block dgamma / dbeta partials (the library's block cap x 2 x H)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, int(lib.vtx_layernorm_workspace_floats(c_int(2048)))), dtype=torch.float32, device=x.device)
-        _ln_ws[_ws_key(x.device)] = ws
-    call("vtx_layernorm_residual_bwd", c_int(dtype_code(x.dtype)), ptr(x), ptr(y), ptr(gamma),
-         ptr(mean), ptr(rstd), ptr(dout), ptr(dz), ptr(dy), ptr(dgamma), ptr(dbeta), ptr(ws), c_int(rows),
-         c_int(H), c_float(p_drop), c_u64(seed), stream_ptr(x))
+    size = _lib.lib().vtx_layernorm_workspace_floats                  # per-block dgamma / dbeta partials (the library's block cap x 2 x H)
+    ws = _scratch(_ln_ws, x.device, size(H), floor=size(2048))
+    call("vtx_layernorm_residual_bwd", dtype_code(x.dtype), ptr(x), ptr(y), ptr(gamma), ptr(mean), ptr(rstd), ptr(dout), ptr(dz),
+         ptr(dy), ptr(dgamma), ptr(dbeta), ptr(ws), rows, H, p_drop, seed, stream_ptr(x))
     return dz, (dy if dy is not None else dz)
 
 
 # ---------------------------------------------------------------------------------------
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
-c_long = _lib.ctypes.c_long
 
 
 _stat_ws = {}
@@ -75,11 +77,7 @@ STAT_WS_FLOATS = 32 * 1024 * 1024      # 128 MB: the epilogue partials [rows / 6
 
 
 def stat_workspace(device):
-    ws = _stat_ws.get(_ws_key(device))
-    if ws is None:
-        ws = torch.empty(STAT_WS_FLOATS if device.type == "cuda" else 1 << 20, dtype=torch.float32, device=device)
-        _stat_ws[_ws_key(device)] = ws
-    return ws
+    return _scratch(_stat_ws, device, 0, floor=STAT_WS_FLOATS if device.type == "cuda" else 1 << 20)
 
 
 class BnStats:
@@ -92,11 +90,11 @@ class BnStats:
 def _stat_args(out_rows, N, bn_shift, device):
     """(parts ptr, shift ptr, strips int*, parts tensor) -- NULLs unless statistics are requested and fit."""
     if bn_shift is None:
-        return ptr(None), ptr(None), None, None
+        return 0, 0, None, None
     ws = stat_workspace(device)
     if ((out_rows + 63) // 64 + 4) * 2 * N > ws.numel():
-        return ptr(None), ptr(None), None, None
-    return ptr(ws), ptr(bn_shift), c_int(0), ws
+        return 0, 0, None, None
+    return ptr(ws), ptr(bn_shift), _lib.ctypes.c_int(0), ws
 
 
 def gemm_nt(a, b, bias=None, residual=None, act=ACT_NONE, want_preact=False, alpha=1.0,
@@ -116,11 +114,9 @@ def gemm_nt(a, b, bias=None, residual=None, act=ACT_NONE, want_preact=False, alp
     if residual is not None:
         assert residual.dim() == 2 and residual.stride(1) == 1 and residual.dtype == odt
     sp, ss, strips, ws = _stat_args(M, N, bn_shift, a.device)
-    call("vtx_gemm_nt", c_int(dtype_code(a.dtype)), c_int(M), c_int(N), c_int(K), ptr(a),
-         c_long(a.stride(0)), ptr(b), c_long(b.stride(0)), ptr(out), c_long(out.stride(0)), ptr(bias),
-         ptr(residual), c_long(residual.stride(0) if residual is not None else 0), ptr(pre),
-         c_int(act), c_float(alpha), c_float(p_drop), c_u64(seed), c_int(1 if out_f32 else 0),
-         sp, ss, (_lib.ctypes.byref(strips) if strips is not None else ptr(None)), stream_ptr(a))
+    call("vtx_gemm_nt", dtype_code(a.dtype), M, N, K, ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(out), out.stride(0),
+         ptr(bias), ptr(residual), residual.stride(0) if residual is not None else 0, ptr(pre), act, alpha, p_drop, seed,
+         1 if out_f32 else 0, sp, ss, (_lib.ctypes.byref(strips) if strips is not None else None), stream_ptr(a))
     if bn_shift is not None:
         st = BnStats(ws, strips.value, bn_shift) if (strips is not None and strips.value > 0) else None
         return out, st
@@ -152,9 +148,8 @@ class BnBwd:
         cap = ((rows + 63) // 64 + 4) * 2 * N
         parts = torch.empty(cap, dtype=torch.float32, device=device)
         # addresses through ptr(): a launch recording (virtex_amd.replay) keeps every tensor a recorded argument points into
-        a = lambda t: ptr(t).value      # noqa: E731  (None -> NULL)
-        d = _BnBwdFusion(a(self.x), a(self.ymask), a(self.mean), a(self.rstd), a(self.gamma), a(self.beta), a(parts), cap, 0,
-                         a(self.ybits))
+        d = _BnBwdFusion(ptr(self.x), ptr(self.ymask), ptr(self.mean), ptr(self.rstd), ptr(self.gamma), ptr(self.beta), ptr(parts),
+                         cap, 0, ptr(self.ybits))
         return d, parts
 
 
@@ -171,8 +166,8 @@ def gemm_nt_bnbwd(a, b, bn: BnBwd, residual=None):
         assert residual.shape == out.shape and residual.is_contiguous() and residual.dtype == a.dtype
     assert bn.x.numel() == M * N and bn.x.is_contiguous() and (bn.ymask is None or bn.ymask.is_contiguous())
     d, parts = bn.descriptor(M, N, a.device)
-    call("vtx_gemm_nt_bnbwd", c_int(dtype_code(a.dtype)), c_int(M), c_int(N), c_int(K), ptr(a), c_long(a.stride(0)),
-         ptr(b), c_long(b.stride(0)), ptr(out), c_long(N), ptr(residual), c_long(N), _lib.ctypes.byref(d), stream_ptr(a))
+    call("vtx_gemm_nt_bnbwd", dtype_code(a.dtype), M, N, K, ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(out), N, ptr(residual),
+         N, _lib.ctypes.byref(d), stream_ptr(a))
     return out, (BnStats(parts, d.strips, None) if d.strips > 0 else None)
 
 
@@ -183,13 +178,7 @@ SPLITK_WS_FLOATS = 64 * 1024 * 1024      # 256 MB of fp32 partial sums per (devi
 def splitk_workspace(device):
     """One scratch buffer per (device, stream): weight-gradient GEMMs may run on a side stream
     concurrently with the main stream's (virtex_amd/modules: `wgrad_stream`)."""
-    key = _ws_key(device)
-    ws = _splitk_ws.get(key)
-    if ws is None:
-        n = SPLITK_WS_FLOATS if device.type == "cuda" else 4 * 1024 * 1024
-        ws = torch.empty(n, dtype=torch.float32, device=device)
-        _splitk_ws[key] = ws
-    return ws
+    return _scratch(_splitk_ws, device, 0, floor=SPLITK_WS_FLOATS if device.type == "cuda" else 4 * 1024 * 1024)
 
 
 class splitk_batch:
@@ -216,13 +205,13 @@ class splitk_batch:
     def end(self):
         if self.open:
             self.open = False
-            call("vtx_splitk_batch_end", _lib.c_void_p(_lib.current_stream_handle(self.device) if self.device.type == "cuda" else 0))
+            call("vtx_splitk_batch_end", _lib._device_stream(self.device))
 
 
 def splitk_flush(device):
     """Inside a splitk_batch: run the pending reductions now (the results of the split-K contractions issued so far are read
     by what follows); a no-op outside a batch."""
-    call("vtx_splitk_batch_flush", _lib.c_void_p(_lib.current_stream_handle(device) if device.type == "cuda" else 0))
+    call("vtx_splitk_batch_flush", _lib._device_stream(device))
 
 
 def gemm_tn_acc(a, b, out, alpha=1.0, split_k=0):
@@ -233,9 +222,8 @@ def gemm_tn_acc(a, b, out, alpha=1.0, split_k=0):
     assert b.shape[0] == K and b.dtype == a.dtype and out.dtype == torch.float32
     assert out.dim() == 2 and out.stride(1) == 1 and out.shape == (M, N)
     ws = splitk_workspace(a.device)
-    call("vtx_gemm_tn_acc", c_int(dtype_code(a.dtype)), c_int(M), c_int(N), c_int(K), ptr(a),
-         c_long(a.stride(0)), ptr(b), c_long(b.stride(0)), ptr(out), c_long(out.stride(0)),
-         c_float(alpha), c_int(split_k), ptr(ws), c_long(ws.numel()), stream_ptr(a))
+    call("vtx_gemm_tn_acc", dtype_code(a.dtype), M, N, K, ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(out), out.stride(0),
+         alpha, split_k, ptr(ws), ws.numel(), stream_ptr(a))
     return out
 
 
@@ -253,9 +241,8 @@ def conv2d_fwd(x, w, stride, pad, bn_shift=None):
     OH, OW = _conv_out(H, W, R, S, stride, pad)
     y = torch.empty(N, OH, OW, KO, dtype=x.dtype, device=x.device)
     sp, ss, strips, ws = _stat_args(N * OH * OW, KO, bn_shift, x.device)
-    call("vtx_conv2d_fwd", c_int(dtype_code(x.dtype)), c_int(N), c_int(H), c_int(W), c_int(C), c_int(KO),
-         c_int(R), c_int(S), c_int(stride), c_int(pad), ptr(x), ptr(w), ptr(y), sp, ss,
-         (_lib.ctypes.byref(strips) if strips is not None else ptr(None)), stream_ptr(x))
+    call("vtx_conv2d_fwd", dtype_code(x.dtype), N, H, W, C, KO, R, S, stride, pad, ptr(x), ptr(w), ptr(y), sp, ss,
+         (_lib.ctypes.byref(strips) if strips is not None else None), stream_ptr(x))
     if bn_shift is not None:
         return y, (BnStats(ws, strips.value, bn_shift) if (strips is not None and strips.value > 0) else None)
     return y
@@ -271,12 +258,11 @@ def conv2d_dgrad(dy, wt, x_shape, stride, pad, residual=None, bn: "BnBwd" = None
     if bn is not None:
         assert bn.x.numel() == dx.numel() and bn.x.is_contiguous() and (bn.ymask is None or bn.ymask.is_contiguous())
         d, parts = bn.descriptor(N * H * W, C, dy.device)
-        call("vtx_conv2d_dgrad_bnbwd", c_int(dtype_code(dy.dtype)), c_int(N), c_int(H), c_int(W), c_int(C), c_int(KO),
-             c_int(R), c_int(S), c_int(stride), c_int(pad), ptr(dy), ptr(wt), ptr(dx), ptr(residual),
-             _lib.ctypes.byref(d), stream_ptr(dy))
+        call("vtx_conv2d_dgrad_bnbwd", dtype_code(dy.dtype), N, H, W, C, KO, R, S, stride, pad, ptr(dy), ptr(wt), ptr(dx),
+             ptr(residual), _lib.ctypes.byref(d), stream_ptr(dy))
         return dx, (BnStats(parts, d.strips, None) if d.strips > 0 else None)
-    call("vtx_conv2d_dgrad", c_int(dtype_code(dy.dtype)), c_int(N), c_int(H), c_int(W), c_int(C), c_int(KO),
-         c_int(R), c_int(S), c_int(stride), c_int(pad), ptr(dy), ptr(wt), ptr(dx), ptr(residual), stream_ptr(dy))
+    call("vtx_conv2d_dgrad", dtype_code(dy.dtype), N, H, W, C, KO, R, S, stride, pad, ptr(dy), ptr(wt), ptr(dx), ptr(residual),
+         stream_ptr(dy))
     return dx
 
 
@@ -287,9 +273,8 @@ def conv2d_wgrad(x, dy, dw, stride, pad, split_k=0):
     assert C2 == C and dy.shape[-1] == KO and dw.dtype == torch.float32
     _chk(x, "x"); _chk(dy, "dy", x.dtype); _chk(dw, "dw")
     ws = splitk_workspace(x.device)
-    call("vtx_conv2d_wgrad", c_int(dtype_code(x.dtype)), c_int(N), c_int(H), c_int(W), c_int(C), c_int(KO),
-         c_int(R), c_int(S), c_int(stride), c_int(pad), ptr(x), ptr(dy), ptr(dw), c_int(split_k), ptr(ws),
-         c_long(ws.numel()), stream_ptr(x))
+    call("vtx_conv2d_wgrad", dtype_code(x.dtype), N, H, W, C, KO, R, S, stride, pad, ptr(x), ptr(dy), ptr(dw), split_k, ptr(ws),
+         ws.numel(), stream_ptr(x))
     return dw
 
 
@@ -301,15 +286,9 @@ _bn_ws = {}
 def bn_workspace(device, C):
     """fp32 scratch for the per-strip partial sums; one buffer per (device, stream), shared by every BN call
     issued on that stream (they are ordered there)."""
-    lib = _lib.lib()
-    lib.vtx_bn_workspace_floats.restype = _lib.ctypes.c_long
-    need = lib.vtx_bn_workspace_floats(c_int(C))
-    ws = _bn_ws.get(_ws_key(device))
-    if ws is None or ws.numel() < need:
-        # zero-initialised ONCE: the first 64 words are the tickets of bn_fin2_kernel (each launch leaves them at zero again)
-        ws = torch.zeros(max(need, lib.vtx_bn_workspace_floats(c_int(2048))), dtype=torch.float32, device=device)
-        _bn_ws[_ws_key(device)] = ws
-    return ws
+    size = _lib.lib().vtx_bn_workspace_floats
+    # zero-initialised ONCE: the first 64 words are the tickets of bn_fin2_kernel (each launch leaves them at zero again)
+    return _scratch(_bn_ws, device, size(C), floor=size(2048), zeroed=True)
 
 
 def bn_fwd(x, gamma, beta, running_mean, running_var, nbt, eps=1e-5, momentum=0.1, relu=True,
@@ -327,11 +306,10 @@ def bn_fwd(x, gamma, beta, running_mean, running_var, nbt, eps=1e-5, momentum=0.
     if want_bits:
         assert relu and x.dtype == torch.bfloat16 and x.numel() % 8 == 0
         bits = torch.empty(x.numel() // 8, dtype=torch.uint8, device=x.device)
-    call("vtx_bn_fwd", c_int(dtype_code(x.dtype)), ptr(x), ptr(residual), ptr(gamma), ptr(beta),
-         ptr(running_mean), ptr(running_var), ptr(nbt), ptr(y), ptr(mean), ptr(rstd), ptr(ws), c_int(P),
-         c_int(C), c_float(eps), c_float(momentum), c_int(1 if relu else 0),
-         ptr(stats.parts if stats else None), c_int(stats.strips if stats else 0),
-         ptr(stats.shift if stats else None), ptr(bits), stream_ptr(x))
+    call("vtx_bn_fwd", dtype_code(x.dtype), ptr(x), ptr(residual), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
+         ptr(nbt), ptr(y), ptr(mean), ptr(rstd), ptr(ws), P, C, eps, momentum, 1 if relu else 0,
+         ptr(stats.parts if stats else None), stats.strips if stats else 0, ptr(stats.shift if stats else None), ptr(bits),
+         stream_ptr(x))
     return (y, mean, rstd, bits) if want_bits else (y, mean, rstd)
 
 
@@ -344,8 +322,8 @@ def bn_bwd(x, dy, ymask, gamma, mean, rstd, dgamma, dbeta, want_dz=False, relu_b
     ws = bn_workspace(x.device, C)
     dx = torch.empty_like(x)
     dz = torch.empty_like(x) if want_dz else None
-    call("vtx_bn_bwd", c_int(dtype_code(x.dtype)), ptr(x), ptr(dy), ptr(ymask), ptr(gamma), ptr(relu_beta), ptr(mean),
-         ptr(rstd), ptr(dx), ptr(dz), ptr(dgamma), ptr(dbeta), ptr(ws), c_int(P), c_int(C), stream_ptr(x))
+    call("vtx_bn_bwd", dtype_code(x.dtype), ptr(x), ptr(dy), ptr(ymask), ptr(gamma), ptr(relu_beta), ptr(mean), ptr(rstd),
+         ptr(dx), ptr(dz), ptr(dgamma), ptr(dbeta), ptr(ws), P, C, stream_ptr(x))
     return (dx, dz) if want_dz else dx
 
 
@@ -357,8 +335,8 @@ def bn_bwd_fused(x, dz, gamma, mean, rstd, dgamma, dbeta, stats: "BnStats"):
     _chk(x, "x"); _chk(dz, "dz", x.dtype)
     ws = bn_workspace(x.device, C)
     dx = torch.empty_like(x)
-    call("vtx_bn_bwd_fused", c_int(dtype_code(x.dtype)), ptr(x), ptr(dz), ptr(gamma), ptr(mean), ptr(rstd),
-         ptr(stats.parts), c_int(stats.strips), ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ws), c_int(P), c_int(C), stream_ptr(x))
+    call("vtx_bn_bwd_fused", dtype_code(x.dtype), ptr(x), ptr(dz), ptr(gamma), ptr(mean), ptr(rstd), ptr(stats.parts),
+         stats.strips, ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ws), P, C, stream_ptr(x))
     return dx
 
 
@@ -367,7 +345,7 @@ def conv3_bwd_fused_supported(dz, wt):
     if dz.dtype != torch.bfloat16:
         return False
     K = dz.shape[-1]
-    return bool(_lib.lib().vtx_conv3_bwd_fused_supported(c_int(dtype_code(dz.dtype)), c_int(dz.numel() // K), c_int(K), c_int(wt.shape[0])))
+    return bool(_lib.lib().vtx_conv3_bwd_fused_supported(dtype_code(dz.dtype), dz.numel() // K, K, wt.shape[0]))
 
 
 def conv3_bwd_fused(dz, x3, gamma3, mean3, rstd3, dgamma3, dbeta3, stats3: "BnStats", wt, bn2: "BnBwd"):
@@ -381,16 +359,15 @@ def conv3_bwd_fused(dz, x3, gamma3, mean3, rstd3, dgamma3, dbeta3, stats3: "BnSt
     assert x3.numel() == dz.numel() and wt.shape == (N, K) and bn2.x.numel() == M * N and bn2.x.is_contiguous()
     assert bn2.gamma is not None and bn2.beta is not None and bn2.ymask is None and bn2.ybits is None
     lib = _lib.lib()
-    nparts = lib.vtx_conv3_bwd_fused_parts(c_int(M))
+    nparts = lib.vtx_conv3_bwd_fused_parts(M)
     dw_parts = torch.empty(nparts, K, N, dtype=torch.float32, device=dz.device)
     dy2 = torch.empty(*dz.shape[:-1], N, dtype=dz.dtype, device=dz.device)
     d, parts = bn2.descriptor(M, N, dz.device)
     ws = bn_workspace(dz.device, K)
-    got = c_int(0)
-    call("vtx_conv3_bwd_fused", c_int(dtype_code(dz.dtype)), c_int(M), c_int(K), c_int(N), ptr(dz), ptr(x3), ptr(gamma3),
-         ptr(mean3), ptr(rstd3), ptr(stats3.parts), c_int(stats3.strips), ptr(dgamma3), ptr(dbeta3), ptr(ws), ptr(wt),
-         c_long(wt.stride(0)), _lib.ctypes.byref(d), ptr(dy2), ptr(dw_parts), c_long(dw_parts.numel()),
-         _lib.ctypes.byref(got), stream_ptr(dz))
+    got = _lib.ctypes.c_int(0)
+    call("vtx_conv3_bwd_fused", dtype_code(dz.dtype), M, K, N, ptr(dz), ptr(x3), ptr(gamma3), ptr(mean3), ptr(rstd3),
+         ptr(stats3.parts), stats3.strips, ptr(dgamma3), ptr(dbeta3), ptr(ws), ptr(wt), wt.stride(0), _lib.ctypes.byref(d),
+         ptr(dy2), ptr(dw_parts), dw_parts.numel(), _lib.ctypes.byref(got), stream_ptr(dz))
     return dy2, BnStats(parts, d.strips, None), dw_parts, nparts
 
 
@@ -403,8 +380,8 @@ def bn_bwd_fold(wt, gamma, mean, rstd, dgamma, dbeta, stats: "BnStats", P):
     wa, wb = torch.empty(N, K, dtype=wt.dtype, device=wt.device), torch.empty(N, K, dtype=wt.dtype, device=wt.device)
     bias = torch.empty(N, dtype=torch.float32, device=wt.device)
     abc = torch.empty(3, K, dtype=torch.float32, device=wt.device)
-    call("vtx_bn_bwd_fold", ptr(gamma), ptr(mean), ptr(rstd), ptr(stats.parts), c_int(stats.strips), ptr(dgamma), ptr(dbeta),
-         ptr(ws), c_int(P), c_int(K), ptr(wt), c_long(wt.stride(0)), c_int(N), ptr(wa), ptr(wb), ptr(bias), ptr(abc), stream_ptr(wt))
+    call("vtx_bn_bwd_fold", ptr(gamma), ptr(mean), ptr(rstd), ptr(stats.parts), stats.strips, ptr(dgamma), ptr(dbeta), ptr(ws), P,
+         K, ptr(wt), wt.stride(0), N, ptr(wa), ptr(wb), ptr(bias), ptr(abc), stream_ptr(wt))
     return wa, wb, bias, abc
 
 
@@ -413,7 +390,7 @@ def wgrad_fold_combine(dw, T, WG, s, abc):
     K, N = dw.shape
     assert dw.dtype == torch.float32 and dw.stride(1) == 1 and T.shape == (K, N) and WG.shape == (K, N) and s.shape == (N,)
     _chk(T, "T", torch.float32); _chk(WG, "WG", torch.float32); _chk(s, "s", torch.float32); _chk(abc, "abc", torch.float32)
-    call("vtx_wgrad_fold_combine", ptr(dw), c_long(dw.stride(0)), ptr(T), ptr(WG), ptr(s), ptr(abc), c_int(K), c_int(N), stream_ptr(dw))
+    call("vtx_wgrad_fold_combine", ptr(dw), dw.stride(0), ptr(T), ptr(WG), ptr(s), ptr(abc), K, N, stream_ptr(dw))
     return dw
 
 
@@ -422,7 +399,7 @@ def partials_reduce_acc(parts, nparts, out):
     M, N = out.shape
     assert out.dtype == torch.float32 and out.stride(1) == 1 and parts.dtype == torch.float32 and parts.is_contiguous()
     assert parts.numel() >= nparts * M * N
-    call("vtx_partials_reduce_acc", ptr(parts), c_int(nparts), c_int(M), c_int(N), ptr(out), c_long(out.stride(0)), stream_ptr(out))
+    call("vtx_partials_reduce_acc", ptr(parts), nparts, M, N, ptr(out), out.stride(0), stream_ptr(out))
     return out
 
 
@@ -437,10 +414,9 @@ def bn_fwd_maxpool(x, gamma, beta, running_mean, running_var, nbt, eps=1e-5, mom
     arg = torch.empty(N, OH, OW, C, dtype=torch.uint8, device=x.device)
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     rstd = torch.empty(C, dtype=torch.float32, device=x.device)
-    call("vtx_bn_fwd_maxpool", c_int(dtype_code(x.dtype)), ptr(x), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
-         ptr(nbt), ptr(y), ptr(arg), ptr(mean), ptr(rstd), ptr(ws), c_int(N), c_int(H), c_int(W), c_int(C), c_float(eps),
-         c_float(momentum), ptr(stats.parts if stats else None), c_int(stats.strips if stats else 0),
-         ptr(stats.shift if stats else None), stream_ptr(x))
+    call("vtx_bn_fwd_maxpool", dtype_code(x.dtype), ptr(x), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), ptr(nbt),
+         ptr(y), ptr(arg), ptr(mean), ptr(rstd), ptr(ws), N, H, W, C, eps, momentum, ptr(stats.parts if stats else None),
+         stats.strips if stats else 0, ptr(stats.shift if stats else None), stream_ptr(x))
     return y, arg, mean, rstd
 
 
@@ -450,8 +426,8 @@ def bn_bwd_maxpool(x, dpool, argmax, gamma, beta, mean, rstd, dgamma, dbeta):
     _chk(x, "x"); _chk(dpool, "dpool", x.dtype); _chk(argmax, "argmax", torch.uint8)
     ws = bn_workspace(x.device, C)
     dx = torch.empty_like(x)
-    call("vtx_bn_bwd_maxpool", c_int(dtype_code(x.dtype)), ptr(x), ptr(dpool), ptr(argmax), ptr(gamma), ptr(beta), ptr(mean),
-         ptr(rstd), ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ws), c_int(N), c_int(H), c_int(W), c_int(C), stream_ptr(x))
+    call("vtx_bn_bwd_maxpool", dtype_code(x.dtype), ptr(x), ptr(dpool), ptr(argmax), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd),
+         ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ws), N, H, W, C, stream_ptr(x))
     return dx
 
 
@@ -461,8 +437,7 @@ def maxpool_fwd(x):
     OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty(N, OH, OW, C, dtype=x.dtype, device=x.device)
     arg = torch.empty(N, OH, OW, C, dtype=torch.uint8, device=x.device)
-    call("vtx_maxpool3x3s2_fwd", c_int(dtype_code(x.dtype)), ptr(x), ptr(y), ptr(arg), c_int(N), c_int(H),
-         c_int(W), c_int(C), stream_ptr(x))
+    call("vtx_maxpool3x3s2_fwd", dtype_code(x.dtype), ptr(x), ptr(y), ptr(arg), N, H, W, C, stream_ptr(x))
     return y, arg
 
 
@@ -470,8 +445,7 @@ def maxpool_bwd(dy, arg, x_shape):
     N, H, W, C = x_shape
     _chk(dy, "dy")
     dx = torch.empty(N, H, W, C, dtype=dy.dtype, device=dy.device)
-    call("vtx_maxpool3x3s2_bwd", c_int(dtype_code(dy.dtype)), ptr(dy), ptr(arg), ptr(dx), c_int(N), c_int(H),
-         c_int(W), c_int(C), stream_ptr(dy))
+    call("vtx_maxpool3x3s2_bwd", dtype_code(dy.dtype), ptr(dy), ptr(arg), ptr(dx), N, H, W, C, stream_ptr(dy))
     return dx
 
 
@@ -480,8 +454,7 @@ def image_to_nhwc(image, dtype, cpad=8, halo=0):
     N, Cin, H, W = image.shape
     _chk(image, "image", torch.float32)
     out = torch.empty(N, H + 2 * halo, W + 2 * halo, cpad, dtype=dtype, device=image.device)
-    call("vtx_image_to_nhwc_halo", c_int(dtype_code(dtype)), ptr(image), ptr(out), c_int(N), c_int(Cin), c_int(H),
-         c_int(W), c_int(cpad), c_int(halo), stream_ptr(image))
+    call("vtx_image_to_nhwc_halo", dtype_code(dtype), ptr(image), ptr(out), N, Cin, H, W, cpad, halo, stream_ptr(image))
     return out
 
 
@@ -494,8 +467,7 @@ def weight_prep(w32, dtype, cpad=None, want_w=True, want_wt=True):
     Cp = cpad or C
     w = torch.empty(KO, T, Cp, dtype=dtype, device=w32.device) if want_w else None
     wt = torch.empty(Cp, T, KO, dtype=dtype, device=w32.device) if want_wt else None
-    call("vtx_weight_prep", c_int(dtype_code(dtype)), ptr(w32), ptr(w), ptr(wt), c_int(KO), c_int(T), c_int(C),
-         c_int(Cp), stream_ptr(w32))
+    call("vtx_weight_prep", dtype_code(dtype), ptr(w32), ptr(w), ptr(wt), KO, T, C, Cp, stream_ptr(w32))
     return w, wt
 
 
@@ -520,8 +492,8 @@ def image_u8_to_nhwc(images, dtype, cpad, size=None, crop_xy=None, flip=None, me
     ctypes = _lib.ctypes
     m = (ctypes.c_float * 3)(*mean)
     sd = (ctypes.c_float * 3)(*std)
-    call("vtx_image_u8_to_nhwc", c_int(dtype_code(dtype)), ptr(images), ptr(out), c_int(N), c_int(Hs), c_int(Ws), c_int(H),
-         c_int(W), c_int(cpad), c_int(halo), ptr(crop_xy), ptr(flip), m, sd, stream_ptr(images))
+    call("vtx_image_u8_to_nhwc", dtype_code(dtype), ptr(images), ptr(out), N, Hs, Ws, H, W, cpad, halo, ptr(crop_xy), ptr(flip),
+         m, sd, stream_ptr(images))
     return out
 
 
@@ -536,8 +508,8 @@ def image_augment_u8(images, params, size, dtype, cpad, halo=0, mean=IMAGENET_CO
     ctypes = _lib.ctypes
     m = (ctypes.c_float * 3)(*mean)
     sd = (ctypes.c_float * 3)(*std)
-    call("vtx_image_augment_u8", c_int(dtype_code(dtype)), ptr(images), ptr(out), ptr(params), ptr(scratch), c_int(N), c_int(Hs),
-         c_int(Ws), c_int(size), c_int(cpad), c_int(halo), m, sd, stream_ptr(images))
+    call("vtx_image_augment_u8", dtype_code(dtype), ptr(images), ptr(out), ptr(params), ptr(scratch), N, Hs, Ws, size, cpad, halo,
+         m, sd, stream_ptr(images))
     return out
 
 
@@ -633,8 +605,7 @@ def prep_many(items, dtype):
                 arr[i] = d
             tab = (torch.from_numpy(arr.view(np.uint8).copy()).to(dev), torch.tensor(starts, dtype=torch.int32, device=dev))
             _prep_tables[sig] = tab
-        call("vtx_weight_prep_batched", c_int(dtype_code(dtype)), ptr(tab[0]), ptr(tab[1]), c_int(len(descs)), c_int(total),
-             stream_ptr(keep[0][3]))
+        call("vtx_weight_prep_batched", dtype_code(dtype), ptr(tab[0]), ptr(tab[1]), len(descs), total, stream_ptr(keep[0][3]))
     for (store, key, param, w32, w, wt) in keep:
         store[key] = ((param._version, param.data_ptr()), w, wt)
     return len(stale)
@@ -650,8 +621,8 @@ def bn_fold(w32, gamma, beta, running_mean, running_var, eps, dtype, cpad=None):
     Cp = cpad or C
     w = torch.empty(KO, T, Cp, dtype=dtype, device=w32.device)
     bias = torch.empty(KO, dtype=torch.float32, device=w32.device)
-    call("vtx_bn_fold", c_int(dtype_code(dtype)), ptr(w32), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
-         c_float(eps), ptr(w), ptr(bias), c_int(KO), c_int(T), c_int(C), c_int(Cp), stream_ptr(w32))
+    call("vtx_bn_fold", dtype_code(dtype), ptr(w32), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), eps, ptr(w),
+         ptr(bias), KO, T, C, Cp, stream_ptr(w32))
     return w, bias
 
 
@@ -666,16 +637,15 @@ def conv2d_infer(x, w, bias, stride, pad, relu=False, residual=None):
     if residual is not None:
         _chk(residual, "residual", x.dtype)
         assert residual.shape == y.shape
-    call("vtx_conv2d_infer", c_int(dtype_code(x.dtype)), c_int(N), c_int(H), c_int(W), c_int(C), c_int(KO),
-         c_int(R), c_int(S), c_int(stride), c_int(pad), ptr(x), ptr(w), ptr(bias), ptr(residual),
-         c_int(1 if relu else 0), ptr(y), stream_ptr(x))
+    call("vtx_conv2d_infer", dtype_code(x.dtype), N, H, W, C, KO, R, S, stride, pad, ptr(x), ptr(w), ptr(bias), ptr(residual),
+         1 if relu else 0, ptr(y), stream_ptr(x))
     return y
 
 
 def cast_from_f32(src, dtype):
     _chk(src, "src", torch.float32)
     out = torch.empty(src.shape, dtype=dtype, device=src.device)
-    call("vtx_cast_from_f32", c_int(dtype_code(dtype)), ptr(src), ptr(out), c_long(src.numel()), stream_ptr(src))
+    call("vtx_cast_from_f32", dtype_code(dtype), ptr(src), ptr(out), src.numel(), stream_ptr(src))
     return out
 
 
@@ -688,9 +658,8 @@ def embedding_fwd(tokens, words, positions, gamma, beta, dtype, padding_idx=0, e
     out = torch.empty(B, T, H, dtype=dtype, device=tokens.device)
     mean = torch.empty(B * T, dtype=torch.float32, device=tokens.device)
     rstd = torch.empty(B * T, dtype=torch.float32, device=tokens.device)
-    call("vtx_embedding_fwd", c_int(dtype_code(dtype)), ptr(tokens), ptr(words), ptr(positions), ptr(gamma),
-         ptr(beta), ptr(out), ptr(mean), ptr(rstd), c_int(B), c_int(T), c_int(H), c_int(V), c_int(padding_idx),
-         c_float(eps), c_float(p_drop), c_u64(seed), stream_ptr(tokens))
+    call("vtx_embedding_fwd", dtype_code(dtype), ptr(tokens), ptr(words), ptr(positions), ptr(gamma), ptr(beta), ptr(out),
+         ptr(mean), ptr(rstd), B, T, H, V, padding_idx, eps, p_drop, seed, stream_ptr(tokens))
     return out, mean, rstd
 
 
@@ -699,9 +668,9 @@ def embedding_bwd(tokens, words, positions, gamma, mean, rstd, dout, dwords, dpo
     B, T = tokens.shape
     V, H = words.shape
     _chk(dout, "dout")
-    call("vtx_embedding_bwd", c_int(dtype_code(dout.dtype)), ptr(tokens), ptr(words), ptr(positions), ptr(gamma),
-         ptr(mean), ptr(rstd), ptr(dout), ptr(dwords), ptr(dpositions), ptr(dgamma), ptr(dbeta), c_int(B),
-         c_int(T), c_int(H), c_int(V), c_int(padding_idx), c_float(p_drop), c_u64(seed), stream_ptr(tokens))
+    call("vtx_embedding_bwd", dtype_code(dout.dtype), ptr(tokens), ptr(words), ptr(positions), ptr(gamma), ptr(mean), ptr(rstd),
+         ptr(dout), ptr(dwords), ptr(dpositions), ptr(dgamma), ptr(dbeta), B, T, H, V, padding_idx, p_drop, seed,
+         stream_ptr(tokens))
 
 
 # ---------------------------------------------------------------------------------------
@@ -710,19 +679,17 @@ def attention_fwd(q, k, v, B, heads, T, S, causal, key_lengths=None, p_drop=0.0,
     for t in (q, k, v):
         assert t.dim() == 2 and t.stride(1) == 1
     o = torch.empty(B * T, heads * 64, dtype=q.dtype, device=q.device)
-    call("vtx_attention_fwd", c_int(dtype_code(q.dtype)), ptr(q), c_long(q.stride(0)), ptr(k), c_long(k.stride(0)),
-         ptr(v), c_long(v.stride(0)), ptr(o), c_long(o.stride(0)), c_int(B), c_int(heads), c_int(T), c_int(S),
-         c_int(64), c_int(1 if causal else 0), ptr(key_lengths), c_float(p_drop), c_u64(seed), stream_ptr(q))
+    call("vtx_attention_fwd", dtype_code(q.dtype), ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(o),
+         o.stride(0), B, heads, T, S, 64, 1 if causal else 0, ptr(key_lengths), p_drop, seed, stream_ptr(q))
     return o
 
 
 def attention_bwd(q, k, v, dout, dq, dk, dv, B, heads, T, S, causal, key_lengths=None, p_drop=0.0, seed=0):
     for t in (q, k, v, dout, dq, dk, dv):
         assert t.dim() == 2 and t.stride(1) == 1
-    call("vtx_attention_bwd", c_int(dtype_code(q.dtype)), ptr(q), c_long(q.stride(0)), ptr(k), c_long(k.stride(0)),
-         ptr(v), c_long(v.stride(0)), ptr(dout), c_long(dout.stride(0)), ptr(dq), c_long(dq.stride(0)), ptr(dk),
-         c_long(dk.stride(0)), ptr(dv), c_long(dv.stride(0)), c_int(B), c_int(heads), c_int(T), c_int(S), c_int(64),
-         c_int(1 if causal else 0), ptr(key_lengths), c_float(p_drop), c_u64(seed), stream_ptr(q))
+    call("vtx_attention_bwd", dtype_code(q.dtype), ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(dout),
+         dout.stride(0), ptr(dq), dq.stride(0), ptr(dk), dk.stride(0), ptr(dv), dv.stride(0), B, heads, T, S, 64,
+         1 if causal else 0, ptr(key_lengths), p_drop, seed, stream_ptr(q))
 
 
 # ---------------------------------------------------------------------------------------
@@ -734,8 +701,8 @@ def cross_entropy_fwd(logits, targets, ignore_index=0):
     lse = torch.empty(R, dtype=torch.float32, device=logits.device)
     row_loss = torch.empty(R, dtype=torch.float32, device=logits.device)
     lc = torch.empty(2, dtype=torch.float32, device=logits.device)
-    call("vtx_cross_entropy_fwd", ptr(logits), c_long(logits.stride(0)), ptr(targets), ptr(lse), ptr(row_loss),
-         ptr(lc), c_int(R), c_int(V), c_int(ignore_index), stream_ptr(logits))
+    call("vtx_cross_entropy_fwd", ptr(logits), logits.stride(0), ptr(targets), ptr(lse), ptr(row_loss), ptr(lc), R, V,
+         ignore_index, stream_ptr(logits))
     return lc, lse
 
 
@@ -743,9 +710,8 @@ def cross_entropy_bwd(logits, targets, lse, lc, grad_out, dtype, ignore_index=0)
     R, V = logits.shape
     _chk(grad_out, "grad_out", torch.float32)
     d = torch.empty(R, V, dtype=dtype, device=logits.device)
-    call("vtx_cross_entropy_bwd", c_int(dtype_code(dtype)), ptr(logits), c_long(logits.stride(0)), ptr(targets),
-         ptr(lse), ptr(lc), ptr(grad_out), ptr(d), c_long(V), c_int(R), c_int(V), c_int(ignore_index),
-         stream_ptr(logits))
+    call("vtx_cross_entropy_bwd", dtype_code(dtype), ptr(logits), logits.stride(0), ptr(targets), ptr(lse), ptr(lc),
+         ptr(grad_out), ptr(d), V, R, V, ignore_index, stream_ptr(logits))
     return d
 
 
@@ -756,7 +722,7 @@ def gap_fwd(x):
     _chk(x, "x")
     B, C = x.shape[0], x.shape[-1]
     y = torch.empty(B, C, dtype=x.dtype, device=x.device)
-    call("vtx_gap_fwd", c_int(dtype_code(x.dtype)), ptr(x), ptr(y), c_int(B), c_int(x.numel() // (B * C)), c_int(C), stream_ptr(x))
+    call("vtx_gap_fwd", dtype_code(x.dtype), ptr(x), ptr(y), B, x.numel() // (B * C), C, stream_ptr(x))
     return y
 
 
@@ -765,13 +731,13 @@ def gap_bwd(dy, HW):
     _chk(dy, "dy")
     B, C = dy.shape
     dx = torch.empty(B, HW, C, dtype=dy.dtype, device=dy.device)
-    call("vtx_gap_bwd", c_int(dtype_code(dy.dtype)), ptr(dy), ptr(dx), c_int(B), c_int(HW), c_int(C), stream_ptr(dy))
+    call("vtx_gap_bwd", dtype_code(dy.dtype), ptr(dy), ptr(dx), B, HW, C, stream_ptr(dy))
     return dx
 
 
 def _ignore_array(ignore):
     ignore = [int(i) for i in ignore]
-    return (_lib.ctypes.c_int * max(len(ignore), 1))(*ignore), c_int(len(ignore))
+    return (_lib.ctypes.c_int * max(len(ignore), 1))(*ignore), len(ignore)
 
 
 def khot_ce_fwd(logits, labels, ignore=(), V=None):
@@ -784,8 +750,8 @@ def khot_ce_fwd(logits, labels, ignore=(), V=None):
     lse, kcount, row_loss = (torch.empty(R, dtype=torch.float32, device=logits.device) for _ in range(3))
     loss = torch.empty(1, dtype=torch.float32, device=logits.device)
     ign, n = _ignore_array(ignore)
-    call("vtx_khot_ce_fwd", ptr(logits), c_long(logits.stride(0)), ptr(labels), c_int(labels.shape[1]), ign, n, ptr(lse),
-         ptr(kcount), ptr(row_loss), ptr(loss), c_int(R), c_int(V), stream_ptr(logits))
+    call("vtx_khot_ce_fwd", ptr(logits), logits.stride(0), ptr(labels), labels.shape[1], ign, n, ptr(lse), ptr(kcount),
+         ptr(row_loss), ptr(loss), R, V, stream_ptr(logits))
     return loss, lse, kcount
 
 
@@ -796,8 +762,8 @@ def khot_ce_bwd(logits, labels, lse, kcount, grad_out, dtype, ignore=(), V=None)
     _chk(grad_out, "grad_out", torch.float32); _chk(labels, "labels", torch.int64)
     d = torch.empty(R, ld, dtype=dtype, device=logits.device)
     ign, n = _ignore_array(ignore)
-    call("vtx_khot_ce_bwd", c_int(dtype_code(dtype)), ptr(logits), c_long(logits.stride(0)), ptr(labels), c_int(labels.shape[1]),
-         ign, n, ptr(lse), ptr(kcount), ptr(grad_out), ptr(d), c_long(ld), c_int(R), c_int(V), stream_ptr(logits))
+    call("vtx_khot_ce_bwd", dtype_code(dtype), ptr(logits), logits.stride(0), ptr(labels), labels.shape[1], ign, n, ptr(lse),
+         ptr(kcount), ptr(grad_out), ptr(d), ld, R, V, stream_ptr(logits))
     return d
 
 
@@ -812,20 +778,14 @@ def tied_ce_fwd(hidden, weight, bias, targets, ignore_index=0):
     V = weight.shape[0]
     assert weight.shape[1] == H and weight.dtype == hidden.dtype
     _chk(targets, "targets", torch.int64); _chk(bias, "bias", torch.float32)
-    lib = _lib.lib()
-    lib.vtx_tied_ce_partial_floats.restype = _lib.ctypes.c_long
-    need = lib.vtx_tied_ce_partial_floats(c_int(R), c_int(V))
-    key = _ws_key(hidden.device)
-    ws = _tied_ce_ws.get(key)
-    if ws is None or ws.numel() < 2 * need + 2 * R:
-        ws = torch.empty(2 * need + 2 * R, dtype=torch.float32, device=hidden.device)
-        _tied_ce_ws[key] = ws
+    need = _lib.lib().vtx_tied_ce_partial_floats(R, V)
+    ws = _scratch(_tied_ce_ws, hidden.device, 2 * need + 2 * R)
     pmax, psum, tgt, row_loss = ws[:need], ws[need: 2 * need], ws[2 * need: 2 * need + R], ws[2 * need + R: 2 * need + 2 * R]
     lse = torch.empty(R, dtype=torch.float32, device=hidden.device)
     lc = torch.empty(2, dtype=torch.float32, device=hidden.device)
-    call("vtx_tied_ce_fwd", c_int(dtype_code(hidden.dtype)), c_int(R), c_int(V), c_int(H), ptr(hidden), c_long(hidden.stride(0)),
-         ptr(weight), c_long(weight.stride(0)), ptr(bias), ptr(targets), c_int(ignore_index), ptr(pmax), ptr(psum), c_long(need),
-         ptr(tgt), ptr(lse), ptr(row_loss), ptr(lc), stream_ptr(hidden))
+    call("vtx_tied_ce_fwd", dtype_code(hidden.dtype), R, V, H, ptr(hidden), hidden.stride(0), ptr(weight), weight.stride(0),
+         ptr(bias), ptr(targets), ignore_index, ptr(pmax), ptr(psum), need, ptr(tgt), ptr(lse), ptr(row_loss), ptr(lc),
+         stream_ptr(hidden))
     return lc, lse
 
 
@@ -835,9 +795,8 @@ def tied_ce_bwd(hidden, weight, bias, targets, lse, lc, grad_out, ignore_index=0
     V = weight.shape[0]
     _chk(grad_out, "grad_out", torch.float32)
     d = torch.empty(R, V, dtype=hidden.dtype, device=hidden.device)
-    call("vtx_tied_ce_bwd", c_int(dtype_code(hidden.dtype)), c_int(R), c_int(V), c_int(H), ptr(hidden), c_long(hidden.stride(0)),
-         ptr(weight), c_long(weight.stride(0)), ptr(bias), ptr(targets), c_int(ignore_index), ptr(lse), ptr(lc), ptr(grad_out),
-         ptr(d), stream_ptr(hidden))
+    call("vtx_tied_ce_bwd", dtype_code(hidden.dtype), R, V, H, ptr(hidden), hidden.stride(0), ptr(weight), weight.stride(0),
+         ptr(bias), ptr(targets), ignore_index, ptr(lse), ptr(lc), ptr(grad_out), ptr(d), stream_ptr(hidden))
     return d
 
 
@@ -851,8 +810,7 @@ def label_compact(labels, ignore_index, V):
     R = labels.numel()
     rows, slot = (torch.empty(R, dtype=torch.int32, device=labels.device) for _ in range(2))
     count = torch.empty(1, dtype=torch.int32, device=labels.device)
-    call("vtx_label_compact", ptr(labels), c_int(ignore_index), c_int(V), ptr(rows), ptr(slot), ptr(count), c_int(R),
-         stream_ptr(labels))
+    call("vtx_label_compact", ptr(labels), ignore_index, V, ptr(rows), ptr(slot), ptr(count), R, stream_ptr(labels))
     return rows, slot, count
 
 
@@ -866,8 +824,8 @@ def rows_pack(hidden, labels, rows, count, cap, ignore_index=0):
         raise _lib.VtxError(f"rows_pack: labels / rows must have the {R} rows of hidden, count one element")
     packed = torch.empty(cap, H, dtype=hidden.dtype, device=hidden.device)
     targets = torch.empty(cap, dtype=torch.int64, device=hidden.device)
-    call("vtx_rows_pack", c_int(dtype_code(hidden.dtype)), ptr(hidden), c_long(hidden.stride(0)), ptr(labels), ptr(rows), ptr(count),
-         c_int(cap), ptr(packed), ptr(targets), c_int(ignore_index), c_int(H), stream_ptr(hidden))
+    call("vtx_rows_pack", dtype_code(hidden.dtype), ptr(hidden), hidden.stride(0), ptr(labels), ptr(rows), ptr(count), cap,
+         ptr(packed), ptr(targets), ignore_index, H, stream_ptr(hidden))
     return packed, targets
 
 
@@ -879,8 +837,8 @@ def rows_unpack(dpacked, slot, out=None):
     if out is None:
         out = torch.empty(R, H, dtype=dpacked.dtype, device=dpacked.device)
     assert out.shape == (R, H) and out.stride(1) == 1 and out.dtype == dpacked.dtype
-    call("vtx_rows_unpack", c_int(dtype_code(dpacked.dtype)), ptr(dpacked), ptr(slot), c_int(cap), ptr(out), c_long(out.stride(0)),
-         c_int(R), c_int(H), stream_ptr(dpacked))
+    call("vtx_rows_unpack", dtype_code(dpacked.dtype), ptr(dpacked), ptr(slot), cap, ptr(out), out.stride(0), R, H,
+         stream_ptr(dpacked))
     return out
 
 
@@ -896,9 +854,8 @@ def beam_step(logits, last, score_in, images, per_node, beam, eos):
     score = torch.empty(images, beam, dtype=torch.float32, device=dev)
     parent = torch.empty(images, beam, dtype=torch.int64, device=dev)
     token = torch.empty(images, beam, dtype=torch.int64, device=dev)
-    call("vtx_beam_step", ptr(logits), c_long(logits.stride(0)), ptr(last), ptr(score_in), c_int(images), c_int(rows // images),
-         c_int(V), c_int(eos), c_int(per_node), c_int(beam), ptr(cand_lp), ptr(cand_tok), ptr(score), ptr(parent), ptr(token),
-         stream_ptr(logits))
+    call("vtx_beam_step", ptr(logits), logits.stride(0), ptr(last), ptr(score_in), images, rows // images, V, eos, per_node, beam,
+         ptr(cand_lp), ptr(cand_tok), ptr(score), ptr(parent), ptr(token), stream_ptr(logits))
     return score, parent, token
 
 
@@ -910,8 +867,8 @@ def nucleus_step(logits, last, u, eos, p):
     _chk(last, "last", torch.int64); _chk(u, "u", torch.float32)
     token = torch.empty(rows, dtype=torch.int64, device=logits.device)
     kept = torch.empty(rows, dtype=torch.int32, device=logits.device)
-    call("vtx_nucleus_step", ptr(logits), c_long(logits.stride(0)), ptr(last), ptr(u), c_int(rows), c_int(V), c_int(eos),
-         c_float(p), ptr(token), ptr(kept), stream_ptr(logits))
+    call("vtx_nucleus_step", ptr(logits), logits.stride(0), ptr(last), ptr(u), rows, V, eos, p, ptr(token), ptr(kept),
+         stream_ptr(logits))
     return token, kept
 
 
@@ -921,12 +878,8 @@ _colsum_ws = {}
 def colsum_acc(x, out):
     assert x.dim() == 2 and x.stride(1) == 1 and out.dtype == torch.float32
     C = x.shape[1]
-    ws = _colsum_ws.get(_ws_key(x.device))
-    if ws is None or ws.numel() < 256 * C:
-        ws = torch.empty(256 * max(C, 10000), dtype=torch.float32, device=x.device)
-        _colsum_ws[_ws_key(x.device)] = ws
-    call("vtx_colsum_acc", c_int(dtype_code(x.dtype)), ptr(x), c_long(x.stride(0)), ptr(out), ptr(ws),
-         c_int(x.shape[0]), c_int(C), stream_ptr(x))
+    ws = _scratch(_colsum_ws, x.device, 256 * C, floor=256 * 10000)
+    call("vtx_colsum_acc", dtype_code(x.dtype), ptr(x), x.stride(0), ptr(out), ptr(ws), x.shape[0], C, stream_ptr(x))
     return out
 
 
@@ -934,15 +887,14 @@ def add(a, b, out=None):
     _chk(a, "a"); _chk(b, "b", a.dtype)
     if out is None:
         out = torch.empty_like(a)
-    call("vtx_add", c_int(dtype_code(a.dtype)), ptr(a), ptr(b), ptr(out), c_long(a.numel()), stream_ptr(a))
+    call("vtx_add", dtype_code(a.dtype), ptr(a), ptr(b), ptr(out), a.numel(), stream_ptr(a))
     return out
 
 
 def gelu_bwd(h, da, p_drop=0.0, seed=0):
     _chk(h, "h"); _chk(da, "da", h.dtype)
     dh = torch.empty_like(h)
-    call("vtx_gelu_bwd", c_int(dtype_code(h.dtype)), ptr(h), ptr(da), ptr(dh), c_long(h.numel()), c_float(p_drop),
-         c_u64(seed), stream_ptr(h))
+    call("vtx_gelu_bwd", dtype_code(h.dtype), ptr(h), ptr(da), ptr(dh), h.numel(), p_drop, seed, stream_ptr(h))
     return dh
 
 
@@ -952,33 +904,31 @@ def dropout_bwd(dx, p_drop, seed):
         return dx
     _chk(dx, "dx")
     dy = torch.empty_like(dx)
-    call("vtx_dropout_bwd", c_int(dtype_code(dx.dtype)), ptr(dx), ptr(dy), c_long(dx.numel()), c_float(p_drop), c_u64(seed),
-         stream_ptr(dx))
+    call("vtx_dropout_bwd", dtype_code(dx.dtype), ptr(dx), ptr(dy), dx.numel(), p_drop, seed, stream_ptr(dx))
     return dy
 
 
 # ---------------------------------------------------------------------------------------
 def sumsq(x, partials, out):
-    call("vtx_sumsq", ptr(x), c_long(x.numel()), ptr(partials), ptr(out), stream_ptr(x))
+    call("vtx_sumsq", ptr(x), x.numel(), ptr(partials), ptr(out), stream_ptr(x))
     return out
 
 
 def sgd_lookahead_step(p, g, m, slow, chunk_off, chunk_len, chunk_seg, seg_lr, seg_wd, lr_mult, momentum,
                        grad_scale, sumsq_buf, max_norm, do_lookahead, alpha, n_elems=0):
     """n_elems: sum of chunk_len (the profiler's algorithmic byte count; 0 = unknown)"""
-    call("vtx_sgd_lookahead_step", ptr(p), ptr(g), ptr(m), ptr(slow), ptr(chunk_off), ptr(chunk_len),
-         ptr(chunk_seg), c_int(chunk_off.numel()), c_long(int(n_elems)), ptr(seg_lr), ptr(seg_wd), c_float(lr_mult), c_float(momentum),
-         c_float(grad_scale), ptr(sumsq_buf), c_float(max_norm if max_norm else 0.0),
-         c_int(1 if do_lookahead else 0), c_float(alpha), stream_ptr(p))
+    call("vtx_sgd_lookahead_step", ptr(p), ptr(g), ptr(m), ptr(slow), ptr(chunk_off), ptr(chunk_len), ptr(chunk_seg),
+         chunk_off.numel(), int(n_elems), ptr(seg_lr), ptr(seg_wd), lr_mult, momentum, grad_scale, ptr(sumsq_buf),
+         max_norm if max_norm else 0.0, 1 if do_lookahead else 0, alpha, stream_ptr(p))
 
 
 def sgd_lookahead_step_dev(p, g, m, slow, chunk_off, chunk_len, chunk_seg, seg_lr, seg_wd, sched, momentum, grad_scale,
                            sumsq_buf, max_norm, alpha, n_elems=0):
     """sched: fp32[2] on the device = {LR multiplier, Lookahead-sync flag} of this step (graph-capturable form)"""
     _chk(sched, "sched", torch.float32)
-    call("vtx_sgd_lookahead_step_dev", ptr(p), ptr(g), ptr(m), ptr(slow), ptr(chunk_off), ptr(chunk_len),
-         ptr(chunk_seg), c_int(chunk_off.numel()), c_long(int(n_elems)), ptr(seg_lr), ptr(seg_wd), ptr(sched), c_float(momentum),
-         c_float(grad_scale), ptr(sumsq_buf), c_float(max_norm if max_norm else 0.0), c_float(alpha), stream_ptr(p))
+    call("vtx_sgd_lookahead_step_dev", ptr(p), ptr(g), ptr(m), ptr(slow), ptr(chunk_off), ptr(chunk_len), ptr(chunk_seg),
+         chunk_off.numel(), int(n_elems), ptr(seg_lr), ptr(seg_wd), ptr(sched), momentum, grad_scale, ptr(sumsq_buf),
+         max_norm if max_norm else 0.0, alpha, stream_ptr(p))
 
 
 def set_dropout_epoch(t):
@@ -990,7 +940,7 @@ def set_dropout_epoch(t):
 # per-launch timing of the contraction kernels (bench.py's roofline leg)
 def profile_start(only_class=-1):
     """only_class: index (the "cls" field of profile_stop()'s records) of the one kernel class to time, -1 = all."""
-    call("vtx_profile_select", c_int(only_class))
+    call("vtx_profile_select", only_class)
     call("vtx_profile_start")
 
 
@@ -1006,8 +956,7 @@ def profile_stop():
         name = ctypes.create_string_buffer(512)
         launches = ctypes.c_long(0)
         sec, fl, by = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
-        call("vtx_profile_get", c_int(i), name, c_int(512), ctypes.byref(launches), ctypes.byref(sec),
-             ctypes.byref(fl), ctypes.byref(by))
+        call("vtx_profile_get", i, name, 512, ctypes.byref(launches), ctypes.byref(sec), ctypes.byref(fl), ctypes.byref(by))
         if launches.value:
             out.append({"cls": i, "name": name.value.decode(), "launches": launches.value, "seconds": sec.value,
                         "flops": fl.value, "bytes": by.value})

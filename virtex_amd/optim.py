@@ -13,7 +13,6 @@ synchronisation happens inside ``step()``.  State dicts of both are indexed in `
 order -- the order the reference's OptimizerFactory builds its one-tensor param groups in
 (virtex/factories.py:529-533) -- so checkpoints interchange with the reference's Lookahead(SGD).
 """
-import ctypes
 import math
 import re
 import weakref
@@ -65,7 +64,7 @@ def _epoch_release(key, handle):
     _epoch_refs[key] = max(n, 0)
     if n == 0:
         try:
-            handle.vtx_set_dropout_epoch(ctypes.c_void_p(0))     # on the library that holds the registration
+            handle.vtx_set_dropout_epoch(None)     # on the library that holds the registration
         except Exception:        # interpreter shutdown: the library may already be gone
             pass
 

@@ -6,7 +6,7 @@ images per step, the LIMIT at 64-128 (BASELINE configs 4 and 5).  A hipGraph of 
 SLOWER on ROCm 7.2 (profiles/r04_hipgraph_configs_2_4_5.txt: the captured side-stream branches run one after the other).
 `StepReplay` keeps the eager launches -- same kernels, same three streams, same events -- and removes only the Python:
 
-  record   one eager step runs with every C-ABI call (`_lib.call`: function pointer + ctypes arguments), every stream / event
+  record   one eager step runs with every C-ABI call (`_lib.call`: function pointer + plain argument values), every stream / event
            operation (event record / wait, stream switch, wait_stream) and every ATen operator that launches work (fills,
            copies, the few adds) appended to ONE ordered list; every tensor that took part stays alive, so device addresses in
            the recorded arguments stay valid;
@@ -70,7 +70,7 @@ class Recorder:
         self.ops: List[Callable[[], None]] = []
         self.labels: List[str] = []      # what each op is (C entry point / stream operation / ATen operator): tools/replay_dump.py
         self.at_stream: List[Optional[int]] = []   # id of the calling thread's current stream when the op was recorded (tests)
-        self.keep = []                   # tensors / ctypes objects whose memory the recorded arguments point into
+        self.keep = []                   # tensors whose memory the recorded addresses point into
         self.lock = threading.Lock()
         self.counts = {"kernel": 0, "aten": 0, "stream": 0, "engine_switch": 0, "collective": 0}
         self.cur = _current_stream_key()         # the stream the replay will be on at this point of the list
