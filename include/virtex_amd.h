@@ -266,6 +266,25 @@ int vtx_conv2d_infer(int dtype, int N, int H, int W, int C, int KO, int R, int S
                      const void* x, const void* w, const float* bias /*nullable*/,
                      const void* residual /*nullable*/, int relu, void* y, void* stream);
 
+/* ---- grouped 3x3 / pad-1 convolutions, stride 1 or 2 (csrc/gconv3x3.hip) -----------------
+ * Replace aten::convolution(groups=G) / convolution_backward of conv2 of torchvision's ResNeXt Bottleneck, reached from
+ * virtex/modules/visual_backbones.py:68-74.  C == KO == G * Cg with Cg in {4, 8, 16, 32, 64} and C a multiple of 64; anything
+ * else is VTX_ERR_SHAPE.  x:[N][H][W][C], y/dy:[N][OH][OW][C] (dtype, OH = (H-1)/stride+1), w:[C][3][3][Cg] (dtype), dw the same in
+ * fp32, ACCUMULATED.  H, W are always the extents of x / dx.
+ * vtx_gconv3x3_infer: y = act(gconv(x, w) + bias (+ residual)), the epilogue of vtx_conv2d_infer.
+ * vtx_gconv3x3_dgrad: dx = gconv^T(dy, w) (+ residual); takes the FORWARD-layout weight (the per-group transpose and the tap
+ *     flip happen while a workgroup stages its 64 channels' weights).
+ * vtx_gconv3x3_wgrad: per-workgroup fp32 partials in `workspace` (at least C*9*Cg floats; more lets more workgroups run), folded
+ *     into dw by the split-K reduction in a fixed order: no floating-point atomics, the same bits on every run. */
+int vtx_gconv3x3_fwd(int dtype, int N, int H, int W, int C, int G, int stride, const void* x, const void* w, void* y,
+                     void* stream);
+int vtx_gconv3x3_infer(int dtype, int N, int H, int W, int C, int G, int stride, const void* x, const void* w,
+                       const float* bias /*nullable*/, const void* residual /*nullable*/, int relu, void* y, void* stream);
+int vtx_gconv3x3_dgrad(int dtype, int N, int H, int W, int C, int G, int stride, const void* dy, const void* w, void* dx,
+                       const void* residual /*nullable: dx += */, void* stream);
+int vtx_gconv3x3_wgrad(int dtype, int N, int H, int W, int C, int G, int stride, const void* x, const void* dy, float* dw,
+                       float* workspace, long workspace_floats, void* stream);
+
 /* ---- BatchNorm2d (training) + ReLU + residual on NHWC, x viewed as [P=N*H*W][C] ---------
  * Replaces aten::batch_norm/relu_/add_ (+backward) of torchvision's Bottleneck
  * (visual_backbones.py:68-74): y = act(gamma*(x-mean)*rstd + beta (+ residual)), running

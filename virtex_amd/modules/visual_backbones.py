@@ -23,7 +23,10 @@ from torch import nn
 from .. import gradsink, ops
 
 RESNET_BLOCKS = {"resnet50": ((3, 4, 6, 3), 64), "resnet101": ((3, 4, 23, 3), 64),
-                 "wide_resnet50_2": ((3, 4, 6, 3), 128)}
+                 "wide_resnet50_2": ((3, 4, 6, 3), 128),
+                 # ResNeXt: (blocks, width per group, groups) -- conv2 is a grouped 3x3 (csrc/gconv3x3.hip)
+                 "resnext50_32x4d": ((3, 4, 6, 3), 4, 32), "resnext101_32x8d": ((3, 4, 23, 3), 8, 32),
+                 "resnext101_64x4d": ((3, 4, 23, 3), 4, 64)}
 STEM_CPAD = 8  # generic stem layout: the 3 input channels zero-padded to 8 (one 16-byte bf16 vector)
 # Packed stem layout (even image widths): pixels padded to 4 channels, a zero frame of STEM_HALO pixels written by the
 # input conversion, filter padded 7x7 -> 7x8.  The 7x7/s2/p3 convolution becomes a "valid" 7x8/s2 one whose 16-byte
@@ -77,12 +80,12 @@ STEM_STATS = os.environ.get("VIRTEX_AMD_STEM_STATS", "1") != "0"
 # Parameter containers (torchvision's module tree; they only HOLD parameters/buffers).
 # ----------------------------------------------------------------------------------------
 class _Bottleneck(nn.Module):
-    def __init__(self, cin, planes, stride, base_width, project):
+    def __init__(self, cin, planes, stride, base_width, project, groups=1):
         super().__init__()
-        mid, cout = planes * base_width // 64, planes * 4
+        mid, cout = int(planes * base_width / 64) * groups, planes * 4
         self.conv1 = nn.Conv2d(cin, mid, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(mid)
-        self.conv2 = nn.Conv2d(mid, mid, 3, stride=stride, padding=1, bias=False)
+        self.conv2 = nn.Conv2d(mid, mid, 3, stride=stride, padding=1, groups=groups, bias=False)
         self.bn2 = nn.BatchNorm2d(mid)
         self.conv3 = nn.Conv2d(mid, cout, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(cout)
@@ -99,7 +102,7 @@ class _ResNetParams(nn.Module):
 
     def __init__(self, name: str, zero_init_residual: bool = True):
         super().__init__()
-        blocks, base_width = RESNET_BLOCKS[name]
+        blocks, base_width, groups = (RESNET_BLOCKS[name] + (1,))[:3]
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
@@ -108,7 +111,7 @@ class _ResNetParams(nn.Module):
         for s, (planes, nblk) in enumerate(zip((64, 128, 256, 512), blocks)):
             layer = []
             for b in range(nblk):
-                layer.append(_Bottleneck(cin, planes, 2 if (b == 0 and s > 0) else 1, base_width, b == 0))
+                layer.append(_Bottleneck(cin, planes, 2 if (b == 0 and s > 0) else 1, base_width, b == 0, groups))
                 cin = planes * 4
             setattr(self, f"layer{s + 1}", nn.Sequential(*layer))
         self.avgpool = nn.AdaptiveAvgPool2d(1)
@@ -138,7 +141,8 @@ class _Unit:
     def __init__(self, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool, cin_pad: int = 0):
         self.conv, self.bn, self.relu = conv, bn, relu
         self.k, self.stride, self.pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        self.cin, self.cout = conv.in_channels, conv.out_channels
+        self.groups = conv.groups
+        self.cin, self.cout = conv.in_channels // conv.groups, conv.out_channels       # cin: channels a filter contracts over
         self.cin_pad = cin_pad or self.cin
         self.is_gemm = self.k == 1 and self.stride == 1
 
@@ -182,7 +186,8 @@ class TorchvisionVisualBackbone(VisualBackbone):
         stem, blocks = self._units()
         units = [stem] + [u for blk in blocks for u in blk if u is not None]
         need_grad = any(u.conv.weight.requires_grad or u.bn.weight.requires_grad or u.bn.bias.requires_grad for u in units)
-        return [(u.conv.weight, u.cin_pad, need_grad) for u in units if u is not stem]   # the stem has its own cache
+        # (the stem has its own cache; a grouped convolution's input gradient takes the forward-layout weight: no transposed copy)
+        return [(u.conv.weight, u.cin_pad, need_grad and u.groups == 1) for u in units if u is not stem]
 
     # -- export ---------------------------------------------------------------------------
     _D2_STAGE = {"layer1": "res2", "layer2": "res3", "layer3": "res4", "layer4": "res5"}
@@ -220,7 +225,7 @@ class TorchvisionVisualBackbone(VisualBackbone):
 
         def run(u, a, relu, residual=None, packed=False):
             w, bias = _folded(u, dt, self._stats_epoch, packed)
-            return ops.conv2d_infer(a, w, bias, u.stride, 0 if packed else u.pad, relu=relu, residual=residual)
+            return ops.conv2d_infer(a, w, bias, u.stride, 0 if packed else u.pad, relu=relu, residual=residual, groups=u.groups)
 
         with torch.no_grad():
             a0, packed = _stem_input(image, dt)
@@ -385,6 +390,9 @@ def _folded(u: _Unit, dtype, epoch: int = 0, packed: bool = False):
 def _prep_weight(u: _Unit, dtype, need_wt: bool):
     """fp32 master (KO,C,R,S logical) -> compute copies w (KO,R,S,Cp) and wt (Cp,R,S,KO); cached on the
     parameter until it changes (ops.prepped), normally already refreshed for the whole model by ops.prep_many."""
+    if u.groups > 1:                                   # the grouped input gradient transposes per group while it stages: wt IS w
+        w = ops.prepped(u.conv.weight, dtype, cpad=u.cin_pad, want_w=True, want_wt=False)[0].view(u.cout, u.k, u.k, u.cin_pad)
+        return w, (w if need_wt else None)
     w, wt = ops.prepped(u.conv.weight, dtype, cpad=u.cin_pad, want_w=True, want_wt=need_wt)
     w = w.view(u.cout, u.k, u.k, u.cin_pad)
     if wt is not None:
@@ -411,8 +419,8 @@ def _conv_fwd(u: _Unit, x, w, bn_shift=None):
         y, st = ops.gemm_nt(x.view(-1, C), w.view(u.cout, C), bn_shift=bn_shift)
         return y.view(N, H, W, u.cout), st
     if bn_shift is None:
-        return ops.conv2d_fwd(x, w, u.stride, u.pad), None
-    return ops.conv2d_fwd(x, w, u.stride, u.pad, bn_shift=bn_shift)
+        return ops.conv2d_fwd(x, w, u.stride, u.pad, groups=u.groups), None
+    return ops.conv2d_fwd(x, w, u.stride, u.pad, bn_shift=bn_shift, groups=u.groups)
 
 
 def _conv_dgrad(u: _Unit, dy, wt, x_shape, residual=None, bn=None):
@@ -425,7 +433,7 @@ def _conv_dgrad(u: _Unit, dy, wt, x_shape, residual=None, bn=None):
             out, st = ops.gemm_nt_bnbwd(dy.view(-1, u.cout), wt.view(C, u.cout), bn, residual=r)
             return out.view(N, H, W, C), st
         return ops.gemm_nt(dy.view(-1, u.cout), wt.view(C, u.cout), residual=r).view(N, H, W, C)
-    return ops.conv2d_dgrad(dy, wt, x_shape, u.stride, u.pad, residual=residual, bn=bn)
+    return ops.conv2d_dgrad(dy, wt, x_shape, u.stride, u.pad, residual=residual, bn=bn, groups=u.groups)
 
 
 def _conv_wgrad(u: _Unit, x, dy):
@@ -436,7 +444,7 @@ def _conv_wgrad(u: _Unit, x, dy):
     if u.is_gemm:
         ops.gemm_tn_acc(dy.view(-1, u.cout), x.view(-1, u.cin_pad), dw.view(u.cout, u.cin_pad))
     else:
-        ops.conv2d_wgrad(x, dy, dw, u.stride, u.pad)
+        ops.conv2d_wgrad(x, dy, dw, u.stride, u.pad, groups=u.groups)
     if sink is not None:
         return None
     if u.cin_pad != u.cin:

@@ -233,9 +233,26 @@ def _conv_out(H, W, R, S, stride, pad):
     return (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
 
 
-def conv2d_fwd(x, w, stride, pad, bn_shift=None):
+def _grouped_args(x_shape, w_shape, KO, stride, pad, groups):
+    """The (dtype-less) leading arguments of the vtx_gconv3x3_* entry points; w / dw are (KO, 3, 3, C / groups)."""
+    N, H, W, C = x_shape
+    assert C % groups == 0 and tuple(w_shape) == (C, 3, 3, C // groups) and KO == C and pad == 1, \
+        f"grouped convolutions are 3x3 / pad 1 with C == KO: x {tuple(x_shape)}, w {tuple(w_shape)}, groups {groups}, pad {pad}"
+    return N, H, W, C, groups, stride
+
+
+def conv2d_fwd(x, w, stride, pad, bn_shift=None, groups=1):
+    """groups > 1: w is (KO, 3, 3, C / groups); with bn_shift the answer is (y, None) -- the grouped kernel emits no statistics."""
     N, H, W, C = x.shape
     KO, R, S, C2 = w.shape
+    if groups > 1:
+        assert w.dtype == x.dtype
+        _chk(x, "x"); _chk(w, "w")
+        OH, OW = _conv_out(H, W, 3, 3, stride, pad)
+        y = torch.empty(N, OH, OW, KO, dtype=x.dtype, device=x.device)
+        call("vtx_gconv3x3_fwd", dtype_code(x.dtype), *_grouped_args(x.shape, w.shape, KO, stride, pad, groups), ptr(x), ptr(w), ptr(y),
+             stream_ptr(x))
+        return (y, None) if bn_shift is not None else y
     assert C2 == C and w.dtype == x.dtype
     _chk(x, "x"); _chk(w, "w")
     OH, OW = _conv_out(H, W, R, S, stride, pad)
@@ -248,9 +265,17 @@ def conv2d_fwd(x, w, stride, pad, bn_shift=None):
     return y
 
 
-def conv2d_dgrad(dy, wt, x_shape, stride, pad, residual=None, bn: "BnBwd" = None):
-    """bn given: returns (dx, stats) like gemm_nt_bnbwd -- dx is the masked gradient when stats is not None."""
+def conv2d_dgrad(dy, wt, x_shape, stride, pad, residual=None, bn: "BnBwd" = None, groups=1):
+    """bn given: returns (dx, stats) like gemm_nt_bnbwd -- dx is the masked gradient when stats is not None.
+    groups > 1: `wt` is the FORWARD-layout weight (KO, 3, 3, C / groups); with bn the answer is (plain dx, None)."""
     N, H, W, C = x_shape
+    if groups > 1:
+        assert wt.dtype == dy.dtype and dy.shape[-1] == C
+        _chk(dy, "dy"); _chk(wt, "w"); _chk(residual, "residual", dy.dtype)
+        dx = torch.empty(N, H, W, C, dtype=dy.dtype, device=dy.device)
+        call("vtx_gconv3x3_dgrad", dtype_code(dy.dtype), *_grouped_args(x_shape, wt.shape, dy.shape[-1], stride, pad, groups), ptr(dy),
+             ptr(wt), ptr(dx), ptr(residual), stream_ptr(dy))
+        return (dx, None) if bn is not None else dx
     C2, R, S, KO = wt.shape
     assert C2 == C and dy.shape[-1] == KO and wt.dtype == dy.dtype
     _chk(dy, "dy"); _chk(wt, "wt"); _chk(residual, "residual", dy.dtype)
@@ -266,10 +291,17 @@ def conv2d_dgrad(dy, wt, x_shape, stride, pad, residual=None, bn: "BnBwd" = None
     return dx
 
 
-def conv2d_wgrad(x, dy, dw, stride, pad, split_k=0):
-    """dw (KO,R,S,C) fp32 += weight gradient."""
+def conv2d_wgrad(x, dy, dw, stride, pad, split_k=0, groups=1):
+    """dw (KO,R,S,C) fp32 += weight gradient; groups > 1: dw is (KO, 3, 3, C / groups)."""
     N, H, W, C = x.shape
     KO, R, S, C2 = dw.shape
+    if groups > 1:
+        assert dy.shape[-1] == KO and dw.dtype == torch.float32
+        _chk(x, "x"); _chk(dy, "dy", x.dtype); _chk(dw, "dw")
+        ws = splitk_workspace(x.device)
+        call("vtx_gconv3x3_wgrad", dtype_code(x.dtype), *_grouped_args(x.shape, dw.shape, KO, stride, pad, groups), ptr(x), ptr(dy),
+             ptr(dw), ptr(ws), ws.numel(), stream_ptr(x))
+        return dw
     assert C2 == C and dy.shape[-1] == KO and dw.dtype == torch.float32
     _chk(x, "x"); _chk(dy, "dy", x.dtype); _chk(dw, "dw")
     ws = splitk_workspace(x.device)
@@ -626,17 +658,22 @@ def bn_fold(w32, gamma, beta, running_mean, running_var, eps, dtype, cpad=None):
     return w, bias
 
 
-def conv2d_infer(x, w, bias, stride, pad, relu=False, residual=None):
-    """y = act(conv(x, w) + bias (+ residual)) on NHWC; ReLU (if any) comes after the residual add."""
+def conv2d_infer(x, w, bias, stride, pad, relu=False, residual=None, groups=1):
+    """y = act(conv(x, w) + bias (+ residual)) on NHWC; ReLU (if any) comes after the residual add.
+    groups > 1: w is (KO, 3, 3, C / groups)."""
     N, H, W, C = x.shape
     KO, R, S, C2 = w.shape
-    assert C2 == C and w.dtype == x.dtype
+    assert (C2 == C or groups > 1) and w.dtype == x.dtype
     _chk(x, "x"); _chk(w, "w"); _chk(bias, "bias", torch.float32)
     OH, OW = _conv_out(H, W, R, S, stride, pad)
     y = torch.empty(N, OH, OW, KO, dtype=x.dtype, device=x.device)
     if residual is not None:
         _chk(residual, "residual", x.dtype)
         assert residual.shape == y.shape
+    if groups > 1:
+        call("vtx_gconv3x3_infer", dtype_code(x.dtype), *_grouped_args(x.shape, w.shape, KO, stride, pad, groups), ptr(x), ptr(w),
+             ptr(bias), ptr(residual), 1 if relu else 0, ptr(y), stream_ptr(x))
+        return y
     call("vtx_conv2d_infer", dtype_code(x.dtype), N, H, W, C, KO, R, S, stride, pad, ptr(x), ptr(w), ptr(bias), ptr(residual),
          1 if relu else 0, ptr(y), stream_ptr(x))
     return y
