@@ -1,13 +1,20 @@
-// Fused multi-head attention for the tiny tiles of the caption decoder (tuned for T <= 32 queries,
-// S <= 56 keys, head_dim = 64; larger tiles: the general kernels below): one workgroup per (batch, head); Q/K/V tiles live in LDS, the
-// whole score matrix in LDS, softmax in fp32 with wave64 shuffles.  The backward kernel
-// recomputes the probabilities instead of reading them from HBM.
+// Fused multi-head attention of the caption decoder, head_dim = 64.  The backward kernels recompute the probabilities
+// instead of reading them from HBM.  Three kernel pairs, chosen in vtx_attention_fwd / vtx_attention_bwd:
+//   T <= 32 queries, S <= 56 keys (the tuned tile: 30-token captions over the 7 x 7 grid)
+//       fp32: attn_fwd_kernel / attn_bwd_kernel -- one workgroup per (batch, head); Q/K/V tiles and the whole score matrix
+//             in static LDS, softmax in fp32 with wave64 shuffles
+//       bf16: attn_fwd_mfma_kernel / attn_bwd_mfma_kernel -- one wave per (batch, head) on the matrix cores
+//   anything larger
+//       bf16: attn_fwd_stream_kernel (any T, any S) / attn_bwd_stream_kernel (T <= 64, any S) -- the keys streamed through the
+//             matrix cores in tiles of 64 with an online softmax; LDS and registers do not grow with S
+//       fp32, and the bf16 backward at T > 64: attn_fwd_big_kernel / attn_bwd_big_kernel -- the first scheme with run-time
+//             tile sizes in dynamic LDS; refused when the tiles of one (batch, head) do not fit the device's LDS
 //
 //   P = dropout_p( softmax( Q K^T / sqrt(d) + causal + key_padding ) ),  O = P V
 //
 // Replaces aten::scaled_dot_product_attention (+backward) inside
 // torch.nn.functional.multi_head_attention_forward, called by nn.TransformerDecoderLayer's
-// _sa_block / _mha_block from /root/reference/virtex/modules/textual_heads.py:270-275:
+// _sa_block / _mha_block from the reference's virtex/modules/textual_heads.py:270-275:
 // self-attention gets the causal mask (:261-265) merged with the key-padding mask
 // (:255-256, -inf at j >= caption_length[b]); cross-attention over the 7x7 grid gets none.
 // Q/K/V/O are addressed in place inside the packed projection outputs ([rows][ld] with a
@@ -176,8 +183,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnArgs a, const T* __re
 // ---------------------------------------------------------------------------------------------------------
 // Shapes outside the tuned envelope (T > 32 queries or S > 56 keys: another crop size -- 256 x 256 images give an 8 x 8 grid --
 // or a longer caption limit): the same algorithm with run-time tile sizes in dynamic LDS and a softmax that walks a row in
-// steps of 64 lanes.  A correctness path (the reference takes any shape: scaled_dot_product_attention), not a tuned one;
-// both compute dtypes; bounded by LDS: 4 * (T*64 + 2*S'*65 + T*S') bytes forward, 4 * (2*T*64 + 2*S'*65 + 2*T*S') backward
+// steps of 64 lanes.  A correctness path (the reference takes any shape: scaled_dot_product_attention), not a tuned one:
+// fp32, and the bf16 backward of more than 64 queries (every other bf16 shape: the streaming kernels further down); bounded by LDS: 4 * (T*64 + 2*S'*65 + T*S') bytes forward, 4 * (2*T*64 + 2*S'*65 + 2*T*S') backward
 // (S' = S rounded up to 4) must fit 160 KiB -- e.g. T = 32 with S <= 288 forward / 224 backward (448 x 448 images: S = 196).
 // The dropout mask of element (i, j) of block `bh` is drawn at index bh*T*S + i*S + j in both directions.
 struct BigLds { float *q, *o, *k, *v, *p, *g; };
@@ -645,13 +652,317 @@ __global__ __launch_bounds__(128) void attn_bwd_mfma_kernel(AttnArgs a, const bf
     mfma_coefT_times_tile(sC[wave], sQ[wave], dk + (long)b * a.S * lddk + h * D, lddk, a.S, lane);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// bf16 beyond the tuned tile (another crop size, a longer caption limit, the KV-cached decoding step over a large grid): the
+// same matrix-core scheme with the keys STREAMED through in tiles of 64 and an online softmax, so that neither LDS nor
+// registers grow with S.  Per key tile the scores of a 32-query x 64-key block come from 16 MFMAs in the scores layout above;
+// the running row maximum m and sum l live in registers (one value per lane and 16-query sub-tile: a lane's row is lane & 15
+// in the scores layout AND in the O layout, so rescaling the accumulators by exp(m_old - m_new) is one scalar per lane).
+// Dropout follows the general kernels: the mask of element (i, j) of block `bh` is drawn at bh*T*S + i*S + j and applied to
+// the normalised probability -- here to the unnormalised exponential, which is then divided by the undropped row sum.
+constexpr int KT = SP;                     // keys per streamed tile
+
+__device__ __forceinline__ bf16x8_t lds_frag(const bf16_t* tile, int row, int col) {
+    return *reinterpret_cast<const bf16x8_t*>(tile + row * VROW + col);
+}
+__device__ __forceinline__ bool stream_masked(const AttnArgs& a, int len, int i, int j) {
+    return j >= a.S || j >= len || (a.causal && j > i);
+}
+// one key tile of the online softmax for query sub-tile row i: s[jt][r] (raw scores of keys j0 + 16 jt + 4g + r) -> masked,
+// scaled scores in e[][]; returns the new running maximum (m_old merged with the tile's).  `ref` is the value to subtract:
+// 0 while every key so far was masked (m = -inf), so that no exp(-inf - -inf) is formed.
+__device__ __forceinline__ float stream_row_max(const AttnArgs& a, int len, int i, int j0, int g, const f32x4_t (&s)[4],
+                                                float m_old, float (&e)[4][4]) {
+    float m = m_old;
+#pragma unroll
+    for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            e[jt][r] = stream_masked(a, len, i, j0 + 16 * jt + 4 * g + r) ? -INFINITY : s[jt][r] * a.scale;
+            m = fmaxf(m, e[jt][r]);
+        }
+    return quad_max(m);
+}
+__device__ __forceinline__ float stream_exp(float s, float ref) { return s > -INFINITY ? __expf(s - ref) : 0.f; }
+
+// Forward: one wave per (batch, head, 32-query tile), four independent waves per workgroup, wave barriers only.  Q fragments
+// are loaded once; per key tile the K fragments come straight from global memory and the V tile goes through the wave's own
+// LDS tile (9 KB), requested one tile ahead.  Key tiles no row of the query tile can see (causal, key_lengths) are skipped.
+__global__ __launch_bounds__(256) void attn_fwd_stream_kernel(AttnArgs a, bf16_t* __restrict__ o, int nqt, int nwork) {
+    a.drop = a.drop.resolved();
+    __shared__ __attribute__((aligned(16))) bf16_t sV[4][KT * VROW];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, w = lane & 15, g = lane >> 4;
+    const int item = blockIdx.x * 4 + wave;
+    if (item >= nwork) return;
+    const int bh = item / nqt, q0 = (item % nqt) * 32;
+    const int b = bh / a.heads, h = bh % a.heads;
+    const bf16_t* q = (const bf16_t*)a.q + ((long)b * a.T + q0) * a.ldq + h * D;
+    const bf16_t* k = (const bf16_t*)a.k + (long)b * a.S * a.ldk + h * D;
+    const bf16_t* v = (const bf16_t*)a.v + (long)b * a.S * a.ldv + h * D;
+    const int len = a.lengths ? (int)a.lengths[b] : a.S;
+    int send = len < a.S ? len : a.S;                           // keys [0, send) are visible to some row of this tile
+    if (a.causal && q0 + 32 < send) send = q0 + 32;
+    const int nkt = send > 0 ? (send + KT - 1) / KT : 0;
+    bf16x8_t fq[2][2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int it = 0; it < 2; ++it) fq[ks][it] = ld_frag(q, a.ldq, 16 * it + w, a.T - q0, 32 * ks + 8 * g);
+    TileStage<KT> tv;
+    if (nkt > 0) tv.request(v, a.ldv, a.S, lane);
+    float m[2] = {-INFINITY, -INFINITY}, l[2] = {0.f, 0.f};
+    f32x4_t acc[2][4];
+#pragma unroll
+    for (int it = 0; it < 2; ++it)
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) acc[it][dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    const uint64_t pbase = (uint64_t)bh * (uint64_t)a.T * (uint64_t)a.S;
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int j0 = kt * KT;
+        f32x4_t sc[2][4];
+#pragma unroll
+        for (int it = 0; it < 2; ++it)
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt) sc[it][jt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            bf16x8_t fk[4];
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt) fk[jt] = ld_frag(k + (long)j0 * a.ldk, a.ldk, 16 * jt + w, a.S - j0, 32 * ks + 8 * g);
+#pragma unroll
+            for (int it = 0; it < 2; ++it)
+#pragma unroll
+                for (int jt = 0; jt < 4; ++jt)
+                    sc[it][jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk[jt], fq[ks][it], sc[it][jt], 0, 0, 0);
+        }
+        float p[2][4][4];
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int i = q0 + 16 * it + w;
+            const float mn = stream_row_max(a, len, i, j0, g, sc[it], m[it], p[it]);
+            const float ref = mn > -INFINITY ? mn : 0.f;
+            const float alpha = stream_exp(m[it], ref);
+            const uint64_t rbase = pbase + (uint64_t)i * (uint64_t)a.S + (uint64_t)(j0 + 4 * g);
+            float sum = 0.f;
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float e = stream_exp(p[it][jt][r], ref);
+                    sum += e;
+                    p[it][jt][r] = a.drop.apply(e, rbase + 16 * jt + r);
+                }
+            l[it] = l[it] * alpha + quad_sum(sum);
+            m[it] = mn;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) acc[it][dt] *= alpha;
+        }
+        __builtin_amdgcn_wave_barrier();          // every lane is done reading the previous V tile
+        tv.put(sV[wave], lane);
+        if (kt + 1 < nkt) tv.request(v + (long)(j0 + KT) * a.ldv, a.ldv, a.S - j0 - KT, lane);
+        __builtin_amdgcn_wave_barrier();          // sV written by this wave's own lanes
+        mfma_rows_times_tile(p, sV[wave], lane, acc);
+    }
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const float inv = l[it] > 0.f ? 1.f / l[it] : 0.f;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) acc[it][dt] *= inv;
+    }
+    store_rows(o + ((long)b * a.T + q0) * a.ldo + h * D, a.ldo, a.T - q0, lane, acc);
+}
+
+// scores and dP of a 32-query x 64-key block, both in the scores layout: Q and dO fragments from their LDS tiles (rows past T
+// are zero there), K and V fragments straight from global memory
+__device__ __forceinline__ void stream_scores_dp(const bf16_t* sQ, const bf16_t* sO, const bf16_t* k, long ldk, const bf16_t* v,
+                                                 long ldv, int nk, int lane, f32x4_t (&sc)[2][4], f32x4_t (&dp)[2][4]) {
+    const int w = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int it = 0; it < 2; ++it)
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) sc[it][jt] = dp[it][jt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        bf16x8_t fq[2], fo[2], fk[4], fv[4];
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) {
+            fk[jt] = ld_frag(k, ldk, 16 * jt + w, nk, 32 * ks + 8 * g);
+            fv[jt] = ld_frag(v, ldv, 16 * jt + w, nk, 32 * ks + 8 * g);
+        }
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            fq[it] = lds_frag(sQ, 16 * it + w, 32 * ks + 8 * g);
+            fo[it] = lds_frag(sO, 16 * it + w, 32 * ks + 8 * g);
+        }
+#pragma unroll
+        for (int it = 0; it < 2; ++it)
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt) {
+                sc[it][jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk[jt], fq[it], sc[it][jt], 0, 0, 0);
+                dp[it][jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv[jt], fo[it], dp[it][jt], 0, 0, 0);
+            }
+    }
+}
+// out[j][16 dt + 4g + r] = sum_i coef[i][j] * tile[i][d] over 16 * NIT query rows (coef and tile both in LDS), stored complete
+template <int NIT> __device__ __forceinline__ void mfma_coefT_times_rows(const bf16_t* coef, const bf16_t* tile, bf16_t* dst,
+                                                                         long ld, int nrows, int lane) {
+    const int w = lane & 15, g = lane >> 4;
+    bf16x8_t ft[NIT / 2][4];
+#pragma unroll
+    for (int kk = 0; kk < NIT / 2; ++kk)
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) ft[kk][dt] = tr_frag_std(tile, 16 * dt, 32 * kk + 8 * g, lane);
+#pragma unroll
+    for (int jt = 0; jt < 4; ++jt) {
+        f32x4_t r[4];
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) r[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < NIT / 2; ++kk) {
+            const bf16x8_t fc = tr_frag_std(coef, 16 * jt, 32 * kk + 8 * g, lane);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) r[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ft[kk][dt], fc, r[dt], 0, 0, 0);
+        }
+        const int j = 16 * jt + w;
+        if (j < nrows) {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) st4_bf16(dst + (long)j * ld + 16 * dt + 4 * g, r[dt]);
+        }
+    }
+}
+
+// Backward: one wave (= one workgroup) per (batch, head), T <= 16 * NIT queries.  The ABI passes neither O nor the softmax
+// statistics, so sweep 1 over the key tiles rebuilds m, l and D_i = sum_j P_ij dP_ij online (D is rescaled like l); sweep 2
+// recomputes P and dP per tile, accumulates dQ in registers across the tiles and forms the tile's dK and dV over ALL query
+// rows -- dropout(P) and dS are spilled once to LDS in bf16 and read back transposed -- so every output row is written once, by
+// its owner, in a fixed order: no atomics, bit-identical runs.  Key tiles no query can see get zero gradients without compute.
+// LDS per wave: Q, dO, P, dS tiles of 16 NIT rows + one K tile = (64 NIT + 64) * 144 B = 27 KB (NIT = 2) / 45 KB (NIT = 4).
+template <int NIT>
+__global__ __launch_bounds__(64) void attn_bwd_stream_kernel(AttnArgs a, const bf16_t* __restrict__ dout, bf16_t* __restrict__ dq,
+                                                             bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, long lddq,
+                                                             long lddk, long lddv) {
+    constexpr int TR = 16 * NIT, NP = NIT / 2;
+    a.drop = a.drop.resolved();
+    __shared__ __attribute__((aligned(16))) bf16_t sQ[TR * VROW], sO[TR * VROW], sK[KT * VROW], sP[TR * VROW], sS[TR * VROW];
+    const int lane = threadIdx.x, w = lane & 15, g = lane >> 4;
+    const int bh = blockIdx.x, b = bh / a.heads, h = bh % a.heads;
+    const bf16_t* k = (const bf16_t*)a.k + (long)b * a.S * a.ldk + h * D;
+    const bf16_t* v = (const bf16_t*)a.v + (long)b * a.S * a.ldv + h * D;
+    const int len = a.lengths ? (int)a.lengths[b] : a.S;
+    {
+        TileStage<TR> tq, to;
+        tq.request((const bf16_t*)a.q + (long)b * a.T * a.ldq + h * D, a.ldq, a.T, lane);
+        to.request(dout + (long)b * a.T * a.ldo + h * D, a.ldo, a.T, lane);
+        vtx_loads_issued();
+        tq.put(sQ, lane); to.put(sO, lane);
+    }
+    __builtin_amdgcn_wave_barrier();
+    int send = len < a.S ? len : a.S;                           // keys [0, send) are visible to some query
+    if (a.causal && a.T < send) send = a.T;
+    const int nkt = send > 0 ? (send + KT - 1) / KT : 0;
+    const uint64_t pbase = (uint64_t)bh * (uint64_t)a.T * (uint64_t)a.S;
+    float m[NIT], l[NIT], dd[NIT];
+#pragma unroll
+    for (int I = 0; I < NIT; ++I) { m[I] = -INFINITY; l[I] = 0.f; dd[I] = 0.f; }
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int j0 = kt * KT;
+#pragma unroll
+        for (int ip = 0; ip < NP; ++ip) {
+            f32x4_t sc[2][4], dp[2][4];
+            stream_scores_dp(sQ + 32 * ip * VROW, sO + 32 * ip * VROW, k + (long)j0 * a.ldk, a.ldk, v + (long)j0 * a.ldv, a.ldv,
+                             a.S - j0, lane, sc, dp);
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                const int I = 2 * ip + it, i = 16 * I + w;
+                float s[4][4];
+                const float mn = stream_row_max(a, len, i, j0, g, sc[it], m[I], s);
+                const float ref = mn > -INFINITY ? mn : 0.f;
+                const float alpha = stream_exp(m[I], ref);
+                const uint64_t rbase = pbase + (uint64_t)i * (uint64_t)a.S + (uint64_t)(j0 + 4 * g);
+                float sum = 0.f, dot = 0.f;
+#pragma unroll
+                for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float e = stream_exp(s[jt][r], ref);
+                        sum += e;
+                        dot += e * a.drop.apply(dp[it][jt][r], rbase + 16 * jt + r);
+                    }
+                l[I] = l[I] * alpha + quad_sum(sum);
+                dd[I] = dd[I] * alpha + quad_sum(dot);
+                m[I] = mn;
+            }
+        }
+    }
+#pragma unroll
+    for (int I = 0; I < NIT; ++I) {
+        l[I] = l[I] > 0.f ? 1.f / l[I] : 0.f;     // from here on: 1 / l
+        dd[I] *= l[I];
+        if (!(m[I] > -INFINITY)) m[I] = 0.f;
+    }
+    f32x4_t dqa[NP][2][4];
+#pragma unroll
+    for (int ip = 0; ip < NP; ++ip)
+#pragma unroll
+        for (int it = 0; it < 2; ++it)
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) dqa[ip][it][dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    TileStage<KT> tk;
+    if (nkt > 0) tk.request(k, a.ldk, a.S, lane);
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int j0 = kt * KT;
+        __builtin_amdgcn_wave_barrier();          // every lane is done with the previous tile's K, dropout(P) and dS
+        tk.put(sK, lane);
+        if (kt + 1 < nkt) tk.request(k + (long)(j0 + KT) * a.ldk, a.ldk, a.S - j0 - KT, lane);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int ip = 0; ip < NP; ++ip) {
+            f32x4_t sc[2][4], dp[2][4];
+            stream_scores_dp(sQ + 32 * ip * VROW, sO + 32 * ip * VROW, k + (long)j0 * a.ldk, a.ldk, v + (long)j0 * a.ldv, a.ldv,
+                             a.S - j0, lane, sc, dp);
+            float pd[2][4][4], ds[2][4][4];
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                const int I = 2 * ip + it, i = 16 * I + w;
+                const uint64_t rbase = pbase + (uint64_t)i * (uint64_t)a.S + (uint64_t)(j0 + 4 * g);
+#pragma unroll
+                for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const bool masked = stream_masked(a, len, i, j0 + 16 * jt + 4 * g + r);
+                        const float p = masked ? 0.f : __expf(sc[it][jt][r] * a.scale - m[I]) * l[I];
+                        const float gji = a.drop.apply(dp[it][jt][r], rbase + 16 * jt + r);
+                        pd[it][jt][r] = a.drop.apply(p, rbase + 16 * jt + r);
+                        ds[it][jt][r] = p * (gji - dd[I]) * a.scale;
+                    }
+            }
+            spill_coef(sP + 32 * ip * VROW, pd, lane);
+            spill_coef(sS + 32 * ip * VROW, ds, lane);
+            mfma_rows_times_tile(ds, sK, lane, dqa[ip]);         // dQ[i][d] += sum_j dS[i][j] K[j][d]
+        }
+        __builtin_amdgcn_wave_barrier();
+        mfma_coefT_times_rows<NIT>(sP, sO, dv + ((long)b * a.S + j0) * lddv + h * D, lddv, a.S - j0, lane);
+        mfma_coefT_times_rows<NIT>(sS, sQ, dk + ((long)b * a.S + j0) * lddk + h * D, lddk, a.S - j0, lane);
+    }
+    // keys no query sees: zero gradients (16-byte stores; eight chunks per row)
+    for (int c = nkt * KT * 8 + lane; c < a.S * 8; c += 64) {
+        const long j = (long)b * a.S + (c >> 3);
+        *reinterpret_cast<uint4*>(dk + j * lddk + h * D + (c & 7) * 8) = make_uint4(0u, 0u, 0u, 0u);
+        *reinterpret_cast<uint4*>(dv + j * lddv + h * D + (c & 7) * 8) = make_uint4(0u, 0u, 0u, 0u);
+    }
+#pragma unroll
+    for (int ip = 0; ip < NP; ++ip)
+        store_rows(dq + ((long)b * a.T + 32 * ip) * lddq + h * D, lddq, a.T - 32 * ip, lane, dqa[ip]);
+}
+
 static int check(const char* who, int dtype, int B, int heads, int T, int S, int head_dim) {
     VTX_CHECK(dtype == VTX_BF16 || dtype == VTX_F32, VTX_ERR_DTYPE, "%s: bad dtype", who);
     VTX_CHECK(B >= 0 && heads > 0 && T > 0 && S > 0, VTX_ERR_ARG, "%s: bad shape", who);
     VTX_CHECK(head_dim == D, VTX_ERR_SHAPE, "%s: supports head_dim == 64 (got %d)", who, head_dim);
     return VTX_OK;
 }
-// the tuned kernels take T <= 32, S <= 56; anything else runs on the general kernels while its tiles fit the 160 KiB of LDS
+// the tuned kernels take T <= 32, S <= 56; beyond that bf16 streams the keys (backward: T <= 64) and everything else runs on
+// the general kernels while its tiles fit the 160 KiB of LDS
 // (the limit is the DEVICE's: hipDeviceAttributeMaxSharedMemoryPerBlock of the current device, 160 KiB on gfx950 -- read once;
 // a part with a smaller LDS refuses the shape here with the sizes in the message instead of failing the launch)
 static size_t big_lds_max() {
@@ -707,11 +1018,12 @@ extern "C" int vtx_attention_fwd(int dtype, const void* q, long ldq, const void*
     const double fl_fwd = 4.0 * B * heads * T * S * 64, by_fwd = (double)B * heads * 64 * (2.0 * T + 2.0 * S);
     if (!tuned_shape(T, S)) {
         size_t lds = 0;
-        if (dtype == VTX_BF16) {
+        if (dtype == VTX_BF16) {                  // any T, any S: streamed key tiles
             VTX_CHECK(ldo % 8 == 0, VTX_ERR_SHAPE, "attention_fwd: row strides must be multiples of 8");
-            static std::atomic<long> reserved{0};
-            if ((rc = big_prepare("attention_fwd", attn_fwd_big_kernel<bf16_t>, T, S, false, &lds, reserved))) return rc;
-            VTX_KLAUNCH("attention_fwd", fl_fwd, 2.0 * by_fwd, (attn_fwd_big_kernel<bf16_t>), grid, block, lds, (hipStream_t)stream, a, (bf16_t*)o);
+            const int nqt = vtx_cdiv(T, 32);
+            VTX_CHECK((long)B * heads * nqt < (1L << 31) - 4, VTX_ERR_SHAPE, "attention_fwd: too many (batch, head, query tile) items");
+            VTX_KLAUNCH("attention_fwd", fl_fwd, 2.0 * by_fwd, attn_fwd_stream_kernel, dim3(vtx_cdiv((long)B * heads * nqt, 4)), block, 0,
+                        (hipStream_t)stream, a, (bf16_t*)o, nqt, B * heads * nqt);
         } else {
             static std::atomic<long> reserved{0};
             if ((rc = big_prepare("attention_fwd", attn_fwd_big_kernel<float>, T, S, false, &lds, reserved))) return rc;
@@ -748,6 +1060,16 @@ extern "C" int vtx_attention_bwd(int dtype, const void* q, long ldq, const void*
         size_t lds = 0;
         if (dtype == VTX_BF16) {
             VTX_CHECK(lddq % 8 == 0 && lddk % 8 == 0 && lddv % 8 == 0, VTX_ERR_SHAPE, "attention_bwd: gradient row strides must be multiples of 8");
+            if (T <= 64) {                        // streamed key tiles, any S; dQ accumulators in registers bound T
+                if (T <= 32)
+                    VTX_KLAUNCH("attention_bwd", fl_bwd, 2.0 * by_bwd, (attn_bwd_stream_kernel<2>), grid, dim3(64), 0, (hipStream_t)stream, a,
+                                (const bf16_t*)dout, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv);
+                else
+                    VTX_KLAUNCH("attention_bwd", fl_bwd, 2.0 * by_bwd, (attn_bwd_stream_kernel<4>), grid, dim3(64), 0, (hipStream_t)stream, a,
+                                (const bf16_t*)dout, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv);
+                VTX_LAUNCH_CHECK();
+                return VTX_OK;
+            }
             static std::atomic<long> reserved{0};
             if ((rc = big_prepare("attention_bwd", attn_bwd_big_kernel<bf16_t>, T, S, true, &lds, reserved))) return rc;
             VTX_KLAUNCH("attention_bwd", fl_bwd, 2.0 * by_bwd, (attn_bwd_big_kernel<bf16_t>), grid, block, lds, (hipStream_t)stream, a, (const bf16_t*)dout,
