@@ -109,7 +109,8 @@ def gemm_nt(a, b, bias=None, residual=None, act=ACT_NONE, want_preact=False, alp
     if out is None:
         out = torch.empty(M, N, dtype=odt, device=a.device)
     assert out.dtype == odt
-    pre = torch.empty(M, N, dtype=odt, device=a.device) if want_preact else None
+    # the kernels address the pre-activation with the OUTPUT's row stride (EpiStore: preact + m * ldc + n): same layout as `out`
+    pre = torch.empty_strided((M, N), (out.stride(0), 1), dtype=odt, device=a.device) if want_preact else None
     _chk(bias, "bias", torch.float32)
     if residual is not None:
         assert residual.dim() == 2 and residual.stride(1) == 1 and residual.dtype == odt
