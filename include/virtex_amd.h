@@ -541,6 +541,29 @@ int vtx_sgd_lookahead_step_dev(float* p, const float* g, float* m, float* slow, 
                                const float* seg_wd, const float* sched /*[2], device*/, float momentum, float grad_scale,
                                const float* sumsq, float max_norm, float alpha, void* stream);
 int vtx_set_dropout_epoch(const void* dev_u32);
+/* The reference's other optimizer: clip_grad_norm_ (scripts/pretrain_virtex.py:158) + optim.AdamW with "default values from
+ * PyTorch" over the same one-tensor groups (virtex/factories.py:503-545, OPTIM.OPTIMIZER_NAME "adamw", virtex/config.py:170-186)
+ * + Lookahead (virtex/optim/lookahead.py:82-102), over the chunk table above with a second moment buffer v.  Per element:
+ *   g' = clip * grad_scale * g;  p *= 1 - lr wd;  m += (g' - m)(1 - b1);  v = b2 v + (1 - b2) g' g';
+ *   p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps);  if do_lookahead: slow += alpha (p - slow), p = slow.
+ * The betas are passed as 1 - beta (in (0, 1]; fp32 keeps 0.001 to 6e-8 relative, but log(0.999f) only to 1.3e-5), eps > 0, and
+ * t >= 1 is the number of AdamW steps including this one: the kernel derives both bias corrections from it, nothing
+ * step-dependent is precomputed on the host.  slow may be NULL when do_lookahead is 0 (OPTIM.LOOKAHEAD.USE False). */
+int vtx_adamw_lookahead_step(float* p, const float* g, float* m, float* v, float* slow, const long long* chunk_off,
+                             const int* chunk_len, const int* chunk_seg, int nchunks, long n_elems, const float* seg_lr,
+                             const float* seg_wd, float lr_mult, float one_minus_beta1, float one_minus_beta2, float eps,
+                             int t, float grad_scale, const float* sumsq, float max_norm, int do_lookahead, float alpha,
+                             void* stream);
+/* The same step with every per-step quantity in DEVICE memory: sched = {LR multiplier (lr_scheduler.py:174-183), Lookahead
+ * flag (lookahead.py:93-102), t}.  t rides in the schedule array, not as the device step word plus a by-value offset: the step
+ * word counts the LR schedule and t counts AdamW steps (start_step and a loaded checkpoint move them independently), so the
+ * offset would be a per-run value frozen into a recording.  fp32 holds t exactly up to 2^24.  With slow == NULL the flag is
+ * ignored. */
+int vtx_adamw_lookahead_step_dev(float* p, const float* g, float* m, float* v, float* slow, const long long* chunk_off,
+                                 const int* chunk_len, const int* chunk_seg, int nchunks, long n_elems, const float* seg_lr,
+                                 const float* seg_wd, const float* sched /*[3], device*/, float one_minus_beta1,
+                                 float one_minus_beta2, float eps, float grad_scale, const float* sumsq, float max_norm,
+                                 float alpha, void* stream);
 
 #ifdef __cplusplus
 }

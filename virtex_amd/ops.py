@@ -969,6 +969,27 @@ def sgd_lookahead_step_dev(p, g, m, slow, chunk_off, chunk_len, chunk_seg, seg_l
          max_norm if max_norm else 0.0, alpha, stream_ptr(p))
 
 
+def adamw_lookahead_step(p, g, m, v, slow, chunk_off, chunk_len, chunk_seg, seg_lr, seg_wd, lr_mult, betas, eps, t,
+                         grad_scale, sumsq_buf, max_norm, do_lookahead, alpha, n_elems=0):
+    """torch.optim.AdamW behind the clip, then Lookahead; t: AdamW steps including this one; slow: None without Lookahead.
+    The betas cross the ABI as 1 - beta, formed here in double (include/virtex_amd.h says why)."""
+    call("vtx_adamw_lookahead_step", ptr(p), ptr(g), ptr(m), ptr(v), ptr(slow), ptr(chunk_off), ptr(chunk_len),
+         ptr(chunk_seg), chunk_off.numel(), int(n_elems), ptr(seg_lr), ptr(seg_wd), lr_mult, 1.0 - betas[0], 1.0 - betas[1],
+         eps, int(t), grad_scale, ptr(sumsq_buf), max_norm if max_norm else 0.0, 1 if do_lookahead else 0, alpha,
+         stream_ptr(p))
+
+
+def adamw_lookahead_step_dev(p, g, m, v, slow, chunk_off, chunk_len, chunk_seg, seg_lr, seg_wd, sched, betas, eps,
+                             grad_scale, sumsq_buf, max_norm, alpha, n_elems=0):
+    """sched: fp32[3] on the device = {LR multiplier, Lookahead-sync flag, AdamW step count} of this step"""
+    _chk(sched, "sched", torch.float32)
+    if sched.numel() < 3:
+        raise _lib.VtxError(f"adamw_lookahead_step_dev: sched holds {sched.numel()} values, the kernel reads 3")
+    call("vtx_adamw_lookahead_step_dev", ptr(p), ptr(g), ptr(m), ptr(v), ptr(slow), ptr(chunk_off), ptr(chunk_len),
+         ptr(chunk_seg), chunk_off.numel(), int(n_elems), ptr(seg_lr), ptr(seg_wd), ptr(sched), 1.0 - betas[0],
+         1.0 - betas[1], eps, grad_scale, ptr(sumsq_buf), max_norm if max_norm else 0.0, alpha, stream_ptr(p))
+
+
 def set_dropout_epoch(t):
     """t: int32[1] device tensor (or None) mixed into every dropout seed on the device; the caller increments it per step"""
     call("vtx_set_dropout_epoch", ptr(t))

@@ -12,6 +12,11 @@ kernels over flat buffers (csrc/optim.hip); `PretrainOptimizer` is the same arit
 synchronisation happens inside ``step()``.  State dicts of both are indexed in ``model.named_parameters()``
 order -- the order the reference's OptimizerFactory builds its one-tensor param groups in
 (virtex/factories.py:529-533) -- so checkpoints interchange with the reference's Lookahead(SGD).
+
+``optimizer="adamw"`` on either class is the factory's other product (OPTIM.OPTIMIZER_NAME adamw: optim.AdamW with PyTorch's
+default betas and eps over the same groups, virtex/factories.py:503-545): the fused class runs it with the AdamW kernel of
+csrc/optim.hip, the unfused one on ``torch.optim.AdamW(foreach=True)``; state dicts then have torch.optim.AdamW's layout.
+``lookahead_k=None`` is OPTIM.LOOKAHEAD.USE False.
 """
 import math
 import re
@@ -86,30 +91,59 @@ def lr_multiplier(step: int, total_steps: int, warmup_steps: int) -> float:
     return max(0.0, math.cos(frac * (math.pi / 2)) ** 2)
 
 
+OPTIMIZERS = ("sgd", "adamw")        # OPTIM.OPTIMIZER_NAME of the reference (virtex/factories.py:503-508)
+# per-parameter state of each kind in torch's state-dict layout: what tells an SGD checkpoint from an AdamW one
+_STATE_KEYS = {"sgd": ("momentum_buffer",), "adamw": ("exp_avg", "exp_avg_sq")}
+
+
+def _check_state_kind(sd, kind):
+    """A checkpoint of the other optimizer is refused: its buffers would be dropped silently otherwise."""
+    for other in OPTIMIZERS:
+        if other != kind and any(k in st for st in sd["state"].values() for k in _STATE_KEYS[other]):
+            raise ValueError(f"the optimizer state is {other}'s ({' / '.join(_STATE_KEYS[other])}), this optimizer is {kind}")
+
+
+def _adamw_steps(sd, default):
+    """The one step count of an AdamW state dict (every per-parameter entry carries its own)."""
+    steps = {int(round(float(st["step"]))) for st in sd["state"].values() if "step" in st}
+    if len(steps) > 1:
+        raise ValueError(f"the AdamW state entries disagree on the step count: {sorted(steps)}")
+    return steps.pop() if steps else default
+
+
+def _no_lookahead():
+    return RuntimeError("this optimizer was built with lookahead_k=None (OPTIM.LOOKAHEAD.USE False): it keeps no slow weights")
+
+
 class PretrainOptimizer:
-    """SGD + Lookahead + warm-up/cosine schedule + global-norm clipping in one object."""
+    """SGD or AdamW + Lookahead + warm-up/cosine schedule + global-norm clipping in one object."""
 
     def __init__(self, model: torch.nn.Module, cnn_lr=0.2, lr=0.001, weight_decay=1e-4, momentum=0.9,
                  clip_norm=10.0, lookahead_k=5, lookahead_alpha=0.5, total_steps=500000, warmup_steps=10000,
-                 start_step=0):
-        self.model = model
+                 start_step=0, optimizer="sgd", betas=(0.9, 0.999), eps=1e-8):
+        if optimizer not in OPTIMIZERS:
+            raise KeyError(optimizer)
+        self.model, self.kind = model, optimizer
         groups = param_groups(model.named_parameters(), cnn_lr, lr, weight_decay)
         self.base_lrs = [g["lr"] for g in groups]
-        self.sgd = torch.optim.SGD(groups, momentum=momentum, foreach=True)
-        self.params = [g["params"][0] for g in self.sgd.param_groups]
+        if optimizer == "sgd":
+            self.inner = torch.optim.SGD(groups, momentum=momentum, foreach=True)
+        else:                            # `momentum` is ignored, as the reference ignores SGD_MOMENTUM
+            self.inner = torch.optim.AdamW(groups, betas=betas, eps=eps, foreach=True)
+        self.params = [g["params"][0] for g in self.inner.param_groups]
         self.clip_norm, self.k, self.alpha = clip_norm, lookahead_k, lookahead_alpha
-        self.slow = [p.detach().clone() for p in self.params]
+        self.slow = [p.detach().clone() for p in self.params] if lookahead_k is not None else None
         self.kc, self.step_idx = 0, start_step
         self.total_steps, self.warmup_steps = total_steps, warmup_steps
         self._set_lr()
 
     def _set_lr(self):
         mult = lr_multiplier(self.step_idx, self.total_steps, self.warmup_steps)
-        for g, base in zip(self.sgd.param_groups, self.base_lrs):
+        for g, base in zip(self.inner.param_groups, self.base_lrs):
             g["lr"] = base * mult
 
     def zero_grad(self):
-        self.sgd.zero_grad(set_to_none=False)
+        self.inner.zero_grad(set_to_none=False)
 
     @torch.no_grad()
     def step(self, grad_scale: float = 1.0):
@@ -121,9 +155,9 @@ class PretrainOptimizer:
             torch._foreach_mul_(grads, grad_scale)
         if self.clip_norm is not None:
             torch.nn.utils.clip_grad_norm_(self.params, self.clip_norm, foreach=True)
-        self.sgd.step()
+        self.inner.step()
         self.kc += 1
-        if self.kc >= self.k:
+        if self.k is not None and self.kc >= self.k:
             self.kc = 0
             data = [p.data for p in self.params]
             torch._foreach_mul_(data, self.alpha)
@@ -140,37 +174,52 @@ class PretrainOptimizer:
     #    re-seeds them from the current parameters.
     def state_dict(self):
         groups = []
-        for i, (g, base) in enumerate(zip(self.sgd.param_groups, self.base_lrs)):
+        for i, (g, base) in enumerate(zip(self.inner.param_groups, self.base_lrs)):
             d = {k: v for k, v in g.items() if k != "params"}
             d["initial_lr"] = base
             d["params"] = [i]
             groups.append(d)
-        state = {i: {"momentum_buffer": self.sgd.state[p]["momentum_buffer"]}
-                 for i, p in enumerate(self.params) if "momentum_buffer" in self.sgd.state.get(p, {})}
+        if self.kind == "adamw":         # torch.optim.AdamW's entries as they are: step, exp_avg, exp_avg_sq
+            state = {i: dict(self.inner.state[p]) for i, p in enumerate(self.params) if self.inner.state.get(p)}
+        else:
+            state = {i: {"momentum_buffer": self.inner.state[p]["momentum_buffer"]}
+                     for i, p in enumerate(self.params) if "momentum_buffer" in self.inner.state.get(p, {})}
         return {"state": state, "param_groups": groups,
                 "virtex_amd": {"step": self.step_idx, "k_counter": self.kc}}
 
     def load_state_dict(self, sd):
+        _check_state_kind(sd, self.kind)
+        t = _adamw_steps(sd, 0) if self.kind == "adamw" else None
         for i, p in enumerate(self.params):
             st = sd["state"].get(i, sd["state"].get(str(i)))
-            if st is not None and st.get("momentum_buffer") is not None:
-                self.sgd.state[p]["momentum_buffer"] = st["momentum_buffer"].to(p.device, p.dtype).clone()
+            if self.kind == "adamw":
+                if st is not None and st.get("exp_avg") is not None:
+                    self.inner.state[p] = {"step": torch.tensor(float(t)),       # a CPU scalar, as torch.optim.AdamW keeps it
+                                           "exp_avg": st["exp_avg"].to(p.device, p.dtype).clone(),
+                                           "exp_avg_sq": st["exp_avg_sq"].to(p.device, p.dtype).clone()}
+            elif st is not None and st.get("momentum_buffer") is not None:
+                self.inner.state[p]["momentum_buffer"] = st["momentum_buffer"].to(p.device, p.dtype).clone()
         extra = sd.get("virtex_amd", {})
         self.step_idx = int(extra.get("step", self.step_idx))
         self.kc = int(extra.get("k_counter", 0))
-        with torch.no_grad():
-            for s_, p in zip(self.slow, self.params):
-                s_.copy_(p.data)
+        if self.slow is not None:
+            with torch.no_grad():
+                for s_, p in zip(self.slow, self.params):
+                    s_.copy_(p.data)
         self._set_lr()
 
     def load_slow_weights(self):
         """Evaluate on the slow weights (lookahead.py:104-118); undo with restore_fast_weights()."""
+        if self.slow is None:
+            raise _no_lookahead()
         self._backup = [p.detach().clone() for p in self.params]
         with torch.no_grad():
             for p, s_ in zip(self.params, self.slow):
                 p.copy_(s_)          # p.copy_ (not p.data.copy_): bumps p._version, which the compute-weight caches key on
 
     def restore_fast_weights(self):
+        if self.slow is None:
+            raise _no_lookahead()
         with torch.no_grad():
             for p, b in zip(self.params, self._backup):
                 p.copy_(b)
@@ -181,13 +230,23 @@ class FusedPretrainOptimizer:
     """Same arithmetic as `PretrainOptimizer`, executed by two HIP kernels over flat buffers
     (csrc/optim.hip): parameters, gradients (the data-parallel buckets), momentum and Lookahead slow
     weights share one layout; per-parameter learning rate / weight decay come from a segment table.
-    No host synchronisation: the clip coefficient is computed on the device from the squared norm."""
+    No host synchronisation: the clip coefficient is computed on the device from the squared norm.
+
+    ``optimizer="adamw"`` (OPTIM.OPTIMIZER_NAME adamw) runs torch.optim.AdamW's arithmetic in the same place: `flat_m` is
+    the first moment, `flat_v` the second, `t` the number of AdamW steps taken (separate from `step_idx`, which only
+    drives the LR schedule); `momentum` is ignored.  ``lookahead_k=None`` (OPTIM.LOOKAHEAD.USE False) keeps no slow weights."""
 
     def __init__(self, model: torch.nn.Module, buckets, cnn_lr=0.2, lr=0.001, weight_decay=1e-4, momentum=0.9,
                  clip_norm=10.0, lookahead_k=5, lookahead_alpha=0.5, total_steps=500000, warmup_steps=10000,
-                 start_step=0, no_decay=NO_DECAY):
+                 start_step=0, no_decay=NO_DECAY, optimizer="sgd", betas=(0.9, 0.999), eps=1e-8):
         from . import _lib, ops
 
+        if optimizer not in OPTIMIZERS:
+            raise KeyError(optimizer)
+        if optimizer == "sgd" and lookahead_k is None:
+            raise ValueError("the fused SGD step always carries Lookahead; lookahead_k=None is served for optimizer='adamw'")
+        self.kind, self.betas, self.eps = optimizer, (float(betas[0]), float(betas[1])), float(eps)
+        self.t = 0                       # AdamW steps taken: the exponent of the bias corrections
         self.ops = ops
         self.buckets = buckets
         names = {p: n for n, p in model.named_parameters()}
@@ -226,7 +285,11 @@ class FusedPretrainOptimizer:
         self.seg_lr = torch.tensor(seg_lr, dtype=torch.float32, device=dev)
         self.seg_wd = torch.tensor(seg_wd, dtype=torch.float32, device=dev)
         self.flat_m = torch.zeros_like(self.flat_p)
-        self.flat_slow = self.flat_p.clone()
+        self.flat_v = torch.zeros_like(self.flat_p) if optimizer == "adamw" else None
+        self.flat_slow = self.flat_p.clone() if lookahead_k is not None else None
+        if optimizer == "adamw":         # the group keys of the installed torch, not a list written from memory
+            stock = torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], betas=betas, eps=eps)
+            self._group_keys = {k: v for k, v in stock.state_dict()["param_groups"][0].items() if k != "params"}
         self.partials = torch.empty(1024, dtype=torch.float32, device=dev)
         self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self.momentum, self.clip_norm, self.k, self.alpha = momentum, clip_norm, lookahead_k, lookahead_alpha
@@ -254,13 +317,20 @@ class FusedPretrainOptimizer:
             self._device_schedule_step(g, grad_scale)
             return
         self.kc += 1
-        look = self.kc >= self.k
+        look = self.k is not None and self.kc >= self.k
         if look:
             self.kc = 0
         mult = lr_multiplier(self.step_idx, self.total_steps, self.warmup_steps)
-        self.ops.sgd_lookahead_step(self.flat_p, g, self.flat_m, self.flat_slow, self.chunk_off, self.chunk_len,
-                                    self.chunk_seg, self.seg_lr, self.seg_wd, mult, self.momentum, grad_scale,
-                                    self.sumsq, self.clip_norm, look, self.alpha, n_elems=self.n_elems)
+        if self.kind == "adamw":
+            self.t += 1
+            self.ops.adamw_lookahead_step(self.flat_p, g, self.flat_m, self.flat_v, self.flat_slow, self.chunk_off,
+                                          self.chunk_len, self.chunk_seg, self.seg_lr, self.seg_wd, mult, self.betas, self.eps,
+                                          self.t, grad_scale, self.sumsq, self.clip_norm, look, self.alpha,
+                                          n_elems=self.n_elems)
+        else:
+            self.ops.sgd_lookahead_step(self.flat_p, g, self.flat_m, self.flat_slow, self.chunk_off, self.chunk_len,
+                                        self.chunk_seg, self.seg_lr, self.seg_wd, mult, self.momentum, grad_scale,
+                                        self.sumsq, self.clip_norm, look, self.alpha, n_elems=self.n_elems)
         # the kernel wrote the parameters behind torch's back: bump their version counters so that everything
         # keyed on them (the eval-mode folded weights, autograd's saved-tensor checks) sees the update
         for p in self.buckets.params:
@@ -280,8 +350,10 @@ class FusedPretrainOptimizer:
         # disable must not re-point or null what the first one's replays read.
         self.dev = {"step": torch.tensor([float(self.step_idx)], dtype=torch.float32, device=d),
                     "kc": torch.tensor([float(self.kc)], dtype=torch.float32, device=d),
-                    "sched": torch.zeros(2, dtype=torch.float32, device=d),
+                    "sched": torch.zeros(3 if self.kind == "adamw" else 2, dtype=torch.float32, device=d),
                     "epoch": None}
+        if self.kind == "adamw":         # the AdamW step count, advanced on the device like "step": a replay keeps counting
+            self.dev["t"] = torch.tensor([float(self.t)], dtype=torch.float32, device=d)
         self.dev["epoch"], key, handle = _epoch_acquire(d, self.ops)
         self._epoch_release = weakref.finalize(self, _epoch_release, key, handle)
 
@@ -298,6 +370,8 @@ class FusedPretrainOptimizer:
         if self.dev is not None:
             self.step_idx = int(round(self.dev["step"].item()))
             self.kc = int(round(self.dev["kc"].item()))
+            if self.kind == "adamw":
+                self.t = int(round(self.dev["t"].item()))
         self._touch()
 
     def _device_schedule_step(self, g, grad_scale):
@@ -309,13 +383,22 @@ class FusedPretrainOptimizer:
         cosm = torch.cos(((st - float(self.warmup_steps)) / span).clamp_(min=0.0) * (math.pi / 2)).square_()
         mult = torch.where(st < float(self.warmup_steps), st / warm, cosm)
         kc.add_(1.0)
-        look = (kc >= float(self.k)).to(torch.float32)
-        kc.mul_(1.0 - look)
         sched[0:1].copy_(mult)
-        sched[1:2].copy_(look)
-        self.ops.sgd_lookahead_step_dev(self.flat_p, g, self.flat_m, self.flat_slow, self.chunk_off, self.chunk_len,
-                                        self.chunk_seg, self.seg_lr, self.seg_wd, sched, self.momentum, grad_scale,
-                                        self.sumsq, self.clip_norm, self.alpha, n_elems=self.n_elems)
+        if self.k is not None:           # without Lookahead sched[1] stays 0 and the counter simply runs, as on the host
+            look = (kc >= float(self.k)).to(torch.float32)
+            kc.mul_(1.0 - look)
+            sched[1:2].copy_(look)
+        if self.kind == "adamw":
+            dv["t"].add_(1.0)
+            sched[2:3].copy_(dv["t"])
+            self.ops.adamw_lookahead_step_dev(self.flat_p, g, self.flat_m, self.flat_v, self.flat_slow, self.chunk_off,
+                                              self.chunk_len, self.chunk_seg, self.seg_lr, self.seg_wd, sched, self.betas,
+                                              self.eps, grad_scale, self.sumsq, self.clip_norm, self.alpha,
+                                              n_elems=self.n_elems)
+        else:
+            self.ops.sgd_lookahead_step_dev(self.flat_p, g, self.flat_m, self.flat_slow, self.chunk_off, self.chunk_len,
+                                            self.chunk_seg, self.seg_lr, self.seg_wd, sched, self.momentum, grad_scale,
+                                            self.sumsq, self.clip_norm, self.alpha, n_elems=self.n_elems)
         st.add_(1.0)
         dv["epoch"].add_(1)
         capturing = self.flat_p.is_cuda and torch.cuda.is_current_stream_capturing()
@@ -323,10 +406,22 @@ class FusedPretrainOptimizer:
             for p in self.buckets.params:
                 torch.autograd.graph.increment_version(p)
             self.step_idx += 1
+            if self.kind == "adamw":
+                self.t += 1
+
+    def state_tensors(self):
+        """Everything a step of this optimizer changes, for the launch recordings' validation (replay.py): parameters, moments,
+        slow weights if any, and the device-side counters (the device schedule must be enabled)."""
+        dv = self.dev
+        moments = [self.flat_m] + ([self.flat_v] if self.kind == "adamw" else [])
+        slow = [self.flat_slow] if self.flat_slow is not None else []
+        counters = [dv["step"], dv["kc"]] + ([dv["t"]] if self.kind == "adamw" else [])
+        return [self.flat_p] + moments + slow + counters + [dv["epoch"]]
 
     # -- checkpointing: same torch.optim.SGD layout as PretrainOptimizer.state_dict() (momentum buffers are
     #    views of the flat buffer in each parameter's logical shape), so checkpoints move freely between
-    #    the reference's Lookahead(SGD), PretrainOptimizer and this class.
+    #    the reference's Lookahead(SGD), PretrainOptimizer and this class.  With optimizer="adamw" it is torch.optim.AdamW's
+    #    layout instead: per parameter {"step", "exp_avg", "exp_avg_sq"}, the group keys of the installed torch.
     def _views(self, flat):
         out, off = [], 0
         for p in self.buckets.params:
@@ -345,45 +440,63 @@ class FusedPretrainOptimizer:
             self.sync_host()
         mult = lr_multiplier(self.step_idx, self.total_steps, self.warmup_steps)
         names = {p: n for n, p in self.model_named()}
-        views = self._views(self.flat_m)
+        views = self._state_views()
         groups, state = [], {}
         for i, p in enumerate(self.named):
             name = names[p]
             lr = self.cnn_lr if "cnn" in name else self.lr
             wd = 0.0 if re.match(self.no_decay, name) else self.weight_decay
-            groups.append({"lr": lr * mult, "momentum": self.momentum, "dampening": 0, "weight_decay": wd,
-                           "nesterov": False, "maximize": False, "foreach": None, "differentiable": False,
-                           "fused": None, "initial_lr": lr, "params": [i]})
+            if self.kind == "adamw":
+                groups.append({**self._group_keys, "lr": lr * mult, "weight_decay": wd, "initial_lr": lr, "params": [i]})
+            else:
+                groups.append({"lr": lr * mult, "momentum": self.momentum, "dampening": 0, "weight_decay": wd,
+                               "nesterov": False, "maximize": False, "foreach": None, "differentiable": False,
+                               "fused": None, "initial_lr": lr, "params": [i]})
             slot = self._slot_of.get(p)
-            if slot is not None:
-                state[i] = {"momentum_buffer": views[slot]}
+            if slot is None:
+                continue
+            if self.kind == "sgd":
+                state[i] = {"momentum_buffer": views["momentum_buffer"][slot]}
+            elif self.t > 0:             # a stock AdamW that has not stepped holds no state either
+                state[i] = {"step": torch.tensor(float(self.t)), **{k: v[slot] for k, v in views.items()}}
         return {"state": state, "param_groups": groups,
                 "virtex_amd": {"step": self.step_idx, "k_counter": self.kc}}
+
+    def _state_views(self):
+        """{state-dict key: per-slot views of the flat buffer that holds it}"""
+        flats = (self.flat_m,) if self.kind == "sgd" else (self.flat_m, self.flat_v)
+        return {k: self._views(f) for k, f in zip(_STATE_KEYS[self.kind], flats)}
 
     @torch.no_grad()
     def load_state_dict(self, sd):
         if len(sd["param_groups"]) != len(self.named):
             raise ValueError(f"optimizer state has {len(sd['param_groups'])} parameter groups, the model has "
                              f"{len(self.named)} named parameters")
-        views = self._views(self.flat_m)
-        for i, p in enumerate(self.named):
-            slot = self._slot_of.get(p)
-            if slot is None:
-                continue
-            st = sd["state"].get(i, sd["state"].get(str(i)))
-            buf = st.get("momentum_buffer") if st is not None else None
-            if buf is not None:
-                if tuple(buf.shape) != tuple(p.shape):
-                    raise ValueError(f"momentum buffer {i} has shape {tuple(buf.shape)}, parameter {tuple(p.shape)}")
-                views[slot].copy_(buf)
-            else:
-                views[slot].zero_()
+        _check_state_kind(sd, self.kind)
+        t = _adamw_steps(sd, 0) if self.kind == "adamw" else 0      # checked before any buffer is overwritten
+        for key, views in self._state_views().items():
+            for i, p in enumerate(self.named):
+                slot = self._slot_of.get(p)
+                if slot is None:
+                    continue
+                st = sd["state"].get(i, sd["state"].get(str(i)))
+                buf = st.get(key) if st is not None else None
+                if buf is not None:
+                    if tuple(buf.shape) != tuple(p.shape):
+                        raise ValueError(f"{key} {i} has shape {tuple(buf.shape)}, parameter {tuple(p.shape)}")
+                    views[slot].copy_(buf)
+                else:
+                    views[slot].zero_()
         extra = sd.get("virtex_amd", {})
         self.step_idx = int(extra.get("step", self.step_idx))
         self.kc = int(extra.get("k_counter", 0))
+        self.t = t
         if self.dev is not None:
             self.dev["step"].fill_(float(self.step_idx)); self.dev["kc"].fill_(float(self.kc))
-        self.flat_slow.copy_(self.flat_p)        # reference semantics: slow weights restart from the loaded ones
+            if self.kind == "adamw":
+                self.dev["t"].fill_(float(self.t))
+        if self.flat_slow is not None:
+            self.flat_slow.copy_(self.flat_p)    # reference semantics: slow weights restart from the loaded ones
 
     def _touch(self):
         for p in self.buckets.params:
@@ -391,12 +504,16 @@ class FusedPretrainOptimizer:
 
     @torch.no_grad()
     def load_slow_weights(self):
+        if self.flat_slow is None:
+            raise _no_lookahead()
         self._backup = self.flat_p.clone()
         self.flat_p.copy_(self.flat_slow)
         self._touch()
 
     @torch.no_grad()
     def restore_fast_weights(self):
+        if self.flat_slow is None:
+            raise _no_lookahead()
         self.flat_p.copy_(self._backup)
         del self._backup
         self._touch()

@@ -370,7 +370,7 @@ class StepReplay:
 
     # ---- validation: eager step vs replayed step from the same state
     def _state(self):
-        ts = [self.opt.flat_p, self.opt.flat_m, self.opt.flat_slow, self.opt.dev["step"], self.opt.dev["kc"], self.opt.dev["epoch"]]
+        ts = self.opt.state_tensors()        # parameters, moments, slow weights if any, device counters: the optimizer knows its own
         ts += [b for b in self.model.buffers()]
         return ts
 
